@@ -9,7 +9,11 @@ forward pass over every (node, dst)) + one engine launch in which every
 replica executes `--hops` forwarding decisions (enqueue or drop), logging
 one decision record per data notification to HBM.
 
-Run: python bench.py [--gpus N --steps K --warmup W] [--preset configK].  N > 1: one process per
+Run: python bench.py [--gpus N --steps K --warmup W] [--preset configK] [--full] [--dump-outputs DIR].
+A plain run sets up, warms up, times the K steps and prints its JSON line; --full adds the CPU
+baseline (the oracle on the host's threads, ~20 s of host work) to that line.  --dump-outputs DIR
+writes what the last timed step left behind (policy, counters, a fixed sample of the decision log)
+as DIR/<name>.npy, identical from run to run with the same arguments.  N > 1: one process per
 GPU over RCCL, either under torch.distributed.run (RANK/WORLD_SIZE set) or
 launched by this script itself (it starts N child ranks before anything
 touches the GPU, then waits for them).  Replicas are sharded (weak scaling:
@@ -84,7 +88,13 @@ def parse(argv=None):
     p.add_argument("--ping-as-obs", type=int, default=None)
     p.add_argument("--policy", default=None, choices=["dq_routing", "dqn_buffer", "sp"],
                    help="in-kernel policy: DQ-routing argmin table (BASELINE configs[1]), DQN-buffer MLP, SP table")
-    p.add_argument("--cpu-baseline", type=int, default=1)
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not need: the CPU baseline (the oracle on "
+                        "the host's threads, same workload) in the line's cpu_baseline")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the last one left for a caller of the timed path as "
+                        "DIR/<name>.npy (dump_outputs: policy, counters, a fixed sample of the decision log)")
+    p.add_argument("--cpu-baseline", type=int, default=1, help="with --full: 0 leaves the CPU baseline out")
     p.add_argument("--cpu-hops", type=int, default=None,
                    help="oracle hops per host thread (cpu_baseline; default 8e6 with a table policy, 1.2e6 with "
                         "the DQN-buffer MLP: ~10-20 s of host work either way)")
@@ -281,6 +291,41 @@ def issue_roofline(topology: str, replicas: int, hops: int, build: str):
     return {k: e[k] for k in keys if k in e}
 
 
+DUMP_LOG_BYTES = 48 << 20     # --dump-outputs: the decision-log sample's share of the 64 MB the dump may take
+DUMP_LOG_REPLICAS = 16
+DUMP_SEED = 20240
+
+
+def dump_outputs(path: str, eng, pol) -> None:
+    """--dump-outputs: the state the last timed step left for a caller of the timed path
+    (PrismaEngine.run with the refreshed policy), as float .npy files under `path`:
+      policy.npy        float32  the policy the last step ran with ([N, N] action table or packed weights)
+      counters.npy      float64  [R, F] PrismaEngine.counters(), one column per field of
+                                 records.COUNTERS_DTYPE in its order (every integer is below 2^53)
+      log_replicas.npy  float64  [n] the replicas whose decision log is kept: a fixed, seeded sample
+      log.npy           float64  [n, slots, 11 + W] PrismaEngine.log_tensor() of those replicas in ring
+                                 order: the scalar fields of records.record_dtype in order, then obs[W]
+    The log sample is at most DUMP_LOG_BYTES (fewer replicas, then the ring's first slots only)."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    np.save(os.path.join(path, "policy.npy"), pol.detach().cpu().numpy().astype(np.float32))
+    cnt = eng.counters()
+    np.save(os.path.join(path, "counters.npy"),
+            np.stack([cnt[f].astype(np.float64) for f in cnt.dtype.names], axis=1))
+    scalars = [f for f in eng.rec_dtype.names if f != "obs"]
+    row = 8 * (len(scalars) + eng.W)
+    slots = min(eng.log_capacity, DUMP_LOG_BYTES // row)
+    n = max(1, min(eng.R, DUMP_LOG_REPLICAS, DUMP_LOG_BYTES // (row * slots)))
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(eng.R, size=n, replace=False))
+    idx = torch.from_numpy(pick).to(eng.torch_device)
+    raw = eng.log_tensor()[idx, :slots].cpu().numpy()                  # [n, slots, rec_bytes] uint8
+    rec = np.ascontiguousarray(raw).view(eng.rec_dtype).reshape(n, slots)
+    cols = [rec[f].astype(np.float64)[..., None] for f in scalars] + [rec["obs"].astype(np.float64)]
+    np.save(os.path.join(path, "log_replicas.npy"), pick.astype(np.float64))
+    np.save(os.path.join(path, "log.npy"), np.concatenate(cols, axis=-1))
+
+
 INIT_ALLOWANCE_S = 240.0      # first `import torch` on a fresh box (1-2 min) + RCCL init
 STEP_BOUND_S = 5.0            # per launch: the slowest BASELINE workload takes ~0.15 s
 CPU_BASELINE_ALLOWANCE_S = 120.0
@@ -301,7 +346,7 @@ def report_stage(stage: str) -> None:
             fh.write(f"{time.time()}\n")
 
 
-def launch_ranks(n: int, deadline_s: float) -> int:
+def launch_ranks(n: int, deadline_s: float, argv=None) -> int:
     """Start n child ranks of this script (one per GPU) and wait for them.  The parent touches no
     GPU (no torch import at all) and does not exec: it runs the ranks as subprocesses with the
     torch.distributed env contract and returns the worst exit status; a failing rank stops the rest.
@@ -319,7 +364,8 @@ def launch_ranks(n: int, deadline_s: float) -> int:
     for r in range(n):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(n), LOCAL_WORLD_SIZE=str(n),
                    MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), PRISMA_BENCH_REPORT_DIR=rep)
-        procs.append(subprocess.Popen([sys.executable, os.path.abspath(__file__), *sys.argv[1:]], env=env))
+        procs.append(subprocess.Popen([sys.executable, os.path.abspath(__file__),
+                                       *(sys.argv[1:] if argv is None else argv)], env=env))
 
     def last_stage(r):
         got = [st for st in RANK_STAGES if os.path.exists(os.path.join(rep, f"rank{r}.{st}"))]
@@ -400,10 +446,10 @@ def rendezvous_only(args, world: int, rank: int) -> None:
     report_stage("done")
 
 
-def main():
-    args = parse()
+def main(argv=None):
+    args = parse(argv)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        sys.exit(launch_ranks(args.gpus, rank_deadline(args)))
+        sys.exit(launch_ranks(args.gpus, rank_deadline(args), argv))
     report_stage("started")
     stall = os.environ.get("PRISMA_BENCH_STALL_RANK")       # test hook: this rank hangs before init
     if stall is not None and stall == os.environ.get("RANK"):
@@ -487,6 +533,7 @@ def measure(args, lf, world, rank, use_dist, backend, coll_dev, dev, local):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    pol = None
     for _ in range(args.steps):
         pol = policy()
         e0 = torch.cuda.Event(enable_timing=True)
@@ -505,6 +552,9 @@ def measure(args, lf, world, rank, use_dist, backend, coll_dev, dev, local):
         tt = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0 and pol is not None:
+        dump_outputs(args.dump_outputs if len(args.lfs) == 1 else os.path.join(args.dump_outputs, f"lf{lf:g}"),
+                     eng, pol)
     c1 = eng.counters()
     hops_local = int((c1["hops_total"] - c0["hops_total"]).sum())
     deg_avg = float(c1["hop_deg_sum"].sum()) / max(1, int(c1["hops"].sum()))   # mean deg(u) over hops
@@ -570,7 +620,7 @@ def measure(args, lf, world, rank, use_dist, backend, coll_dev, dev, local):
             "replicas_total": int(stats["stats"].shape[0]),
             "per_rank_hops_s": [h / elapsed for h in per_rank],
         }
-        if args.cpu_baseline and world == 1:
+        if args.full and args.cpu_baseline and world == 1:
             kind = "mlp" if args.policy == "dqn_buffer" else "table"
             # warm-up equal to the GPU line's (hops per replica before the timed steps)
             warm = args.warmup * args.hops if args.topology == "er256" else 0

@@ -100,6 +100,11 @@ def load_library(path: str = None):
     path = override or LIB_PATH
     if not os.path.exists(path):
         raise PrismaError(f"{path} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'`")
+    # torch first: its wheel carries its own HIP runtime, and the library works on torch's device
+    # memory, so it must bind to that runtime.  Loaded before torch it would pull in the system's
+    # libamdhip64 as a second runtime in the process, which then finds no device (build() followed
+    # by smoke() in one process).
+    import torch  # noqa: F401
     L = C.CDLL(path)
     L.prisma_abi_version.restype = C.c_int
     L.prisma_last_error.restype = C.c_char_p

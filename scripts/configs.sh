@@ -2,12 +2,14 @@
 # One bench line per BASELINE.json config that fits one GPU, appended to
 # gpurun_out/configs.jsonl, through bench.py's presets (per-GPU shares: config 4's 16384 / 8 = 2048
 # GEANT replicas over its load-factor sweep, config 5's 8192 / 8 = 1024 ER-256 replicas).
-# CPU=1: each line also carries its cpu_baseline (the oracle on this host's threads, same workload).
+# CPU=1: bench.py --full, so each line also carries its cpu_baseline (the oracle on this host's
+# threads, same workload).
 set -e
 OUT=gpurun_out/configs.jsonl
 : > $OUT
 C=${CPU:-0}
 B="timeout -k 10 600 python bench.py --steps 5 --warmup 1"
+[ "$C" = 0 ] || B="$B --full"
 echo "config 1: abilene SP, 1 replica" && $B --preset config1 --cpu-baseline $C >> $OUT
 echo "config 2: abilene DQ-routing, 4096" && $B --preset config2 --cpu-baseline $C >> $OUT
 echo "config 3: abilene on geant, DQN-buffer pingAsObs=1, 4096" && $B --preset config3 --cpu-baseline $C >> $OUT

@@ -8,7 +8,7 @@ OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT/sq
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 B="python bench.py --steps 5 --warmup 1 --cpu-baseline 0 $*"
-echo "[1/7] bench" && timeout -k 10 400 python bench.py $* > $OUT/bench.json 2> $OUT/bench.err
+echo "[1/7] bench" && timeout -k 10 400 python bench.py --full $* > $OUT/bench.json 2> $OUT/bench.err
 cat $OUT/bench.json
 echo "[2/7] kernel trace" && timeout -k 10 400 rocprofv3 --kernel-trace --stats -f csv -d $OUT/kt -o run -- $B > $OUT/kt.log 2>&1
 echo "[3/7] pmc FETCH_SIZE" && timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --kernel-include-regex step_kernel -f csv -d $OUT/pmc_fetch -o run -- $B > $OUT/pmc_fetch.log 2>&1

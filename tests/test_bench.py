@@ -32,6 +32,13 @@ def test_presets_and_overrides():
     assert a.cpu_hops == 8000000 and bench.parse(["--preset", "config3"]).cpu_hops == 1200000
 
 
+def test_plain_run_is_the_default_and_full_is_an_option():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 3)
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full and a.cpu_baseline == 1 and a.dump_outputs == "out"
+
+
 def test_cpu_baseline_table_and_mlp(oracle_mod):
     topo = Topology.example("abilene")
     params = engine_params(topo, sim_time_s=2.0, ping_as_obs=1, auto_reset=0, seed=100)
