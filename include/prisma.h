@@ -326,6 +326,31 @@ int prisma_step(prisma_env_t* env, const int32_t* actions, int32_t* obs_out,
 int prisma_run(prisma_env_t* env, int32_t policy, const void* policy_data,
                int32_t max_hops, void* stream);
 
+/* prisma_run with epsilon-greedy exploration: the same contract (policies,
+ * the DQN-buffer repack, auto_reset, the next-episode restart), but every
+ * data decision may replace the policy's action by a uniform pick over the
+ * deciding node's neighbours.  The rule is exact, so a host can restate it:
+ * for the decision with log index d (the numbering of the records' `prev`,
+ * which carries over episode ends), in episode e, at node v of overlay
+ * degree deg, with policy action g, in replica r:
+ *
+ *   c = philox4x32_10(ctr = {d, 0, e, 2}, key = {seed & 0xffffffff, replica_base + r})
+ *   a = ((c[0] >> 8) < explore_thr[v]) ? (uint32)(((uint64)c[1] * deg) >> 32) : g
+ *
+ * explore_thr: device uint32 [n_nodes], indexed by underlay node id,
+ * floor(eps[v] * 2^24 + 0.5) clamped to [0, 2^24]: 0 never explores, 2^24
+ * always does.  It is read during the launch and constant over it; refresh
+ * an epsilon schedule between launches.  Counter word 3 = 2 keeps the draw
+ * apart from the flow start offsets (0) and the send delays (1).
+ * Destination arrivals and control packets draw nothing.  NULL explore_thr:
+ * PRISMA_ERR_ARG.  The exploring kernels exist for the register-resident
+ * engine without the ctrl paths: an env whose prisma_kernel_info reports
+ * ctrl = 1 (train, notify_dest, PRISMA_RNG_NS3, a tunnelled overlay with
+ * log_capacity >= 2^18) or the memory-resident engine gets
+ * PRISMA_ERR_CONFIG. */
+int prisma_run_explore(prisma_env_t* env, int32_t policy, const void* policy_data,
+                       int32_t max_hops, const uint32_t* explore_thr, void* stream);
+
 /* Copy per-replica counters (n_replicas entries) to host memory.
  * Synchronises `stream`. */
 int prisma_read_counters(prisma_env_t* env, prisma_counters_t* host_out,

@@ -118,6 +118,8 @@ struct KParams {
     unsigned char* spare;        // [R][state_bytes] next-episode images (register engine with
                                  // auto_reset), or null
     const uint32_t* rng;         // ns-3 stream mode: the rng table (engine_layout.h kMrgPowers), or null
+    const uint32_t* explore_thr; // [N] epsilon-greedy thresholds (prisma_run_explore, EXPL instances), or
+                                 // null; last, so the other instances' kernarg offsets stay put
 };
 
 // ---------------------------------------------------------------------------
@@ -2477,6 +2479,28 @@ __device__ __forceinline__ void stage_table(unsigned char* lds, const KParams& P
     }
 }
 
+// Epsilon-greedy exploration (prisma_run_explore, the EXPL instances; include/prisma.h states
+// the rule): data decision d of episode e at node v takes a uniform pick over v's deg overlay
+// neighbours instead of the greedy action g when the top 24 bits of its Philox draw fall below
+// thr[v].  Counter word 3 = 2 keeps the draw apart from the flow start offsets (0) and the send
+// delays (1).  d, v and thr[v] are wave-uniform, so the branch is scalar; the rounds run on the
+// vector unit as in flow_next (the values pass through VGPRs) and the two words used come back
+// with readfirstlane.  A node with thr = 0 never explores and skips the draw.
+__device__ __forceinline__ int explore_action(const Sim& S, const Hot& H, const uint32_t* __restrict__ thr,
+                                              uint32_t d, uint32_t v, int g) {
+    v = rfl(v);
+    const uint32_t t = rfl(thr[v]);
+    if (t == 0u) return g;
+    uint32_t c[4] = { rfl(d), 0u, H.episode, 2u };
+    uint32_t k0 = S.lv.seed_lo(), k1 = S.gid;
+    asm volatile("" : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]), "+v"(k0), "+v"(k1));
+    philox4x32_10(c, k0, k1);
+    const uint32_t c0 = rfl(c[0]), c1 = rfl(c[1]);
+    if ((c0 >> 8) >= t) return g;
+    const uint32_t deg = (uint32_t)(t_ovrow(S, v + 1) - t_ovrow(S, v));
+    return (int)(uint32_t)(((uint64_t)c1 * deg) >> 32);
+}
+
 template <int FS, int LS>
 __device__ __forceinline__ void stage_in(unsigned char* lds, const KParams& P, int r, int lane, Regs<FS, LS>& R) {
     CLayout& LC = *(CLayout*)P.lay;
@@ -2554,7 +2578,8 @@ __device__ __forceinline__ bool spare_restart(const KParams&, Sim&, RS&, int, ui
 // then one discrete event per iteration until max_hops hops, a decision that
 // needs an external action, or the end of the episode; publish the outputs.
 // ---------------------------------------------------------------------------
-template <bool MLP, int MB, class RS>
+// EXPL: the fused policy's action goes through explore_action at both decision sites
+template <bool MLP, int MB, bool EXPL = false, class RS>
 __device__ __forceinline__ uint32_t event_loop(const KParams& P, Sim& S, RS& R, int r, uint32_t max_hops) {
     const int lane = S.lane;
     const LV& L = S.lv;
@@ -2577,8 +2602,10 @@ __device__ __forceinline__ uint32_t event_loop(const KParams& P, Sim& S, RS& R, 
         if (table_mode) {
             uint32_t pn = u_ld32(&S.h->pend_node), pd = u_ld32(&S.h->pend_ent[1]);
             MlpPre1 M0;
-            const int a = mlp_mode ? mlp_action<MB>(S, pn, (lane < L.W()) ? S.obs[lane] : 0u, M0)
-                                   : table_action(S, pn * NN + pd);
+            int a = mlp_mode ? mlp_action<MB>(S, pn, (lane < L.W()) ? S.obs[lane] : 0u, M0)
+                             : table_action(S, pn * NN + pd);
+            // (the instances without the ctrl paths: every pending notification is a data decision)
+            if (EXPL) a = explore_action(S, H, P.explore_thr, u_ld32(&S.h->pend_dec), pn, a);
             H.hops_launch += finish_pending(S, R, H, a);
         } else if (P.actions) {
             finish_pending(S, R, H, (int)rfl((uint32_t)P.actions[r]));
@@ -2642,8 +2669,9 @@ __device__ __forceinline__ uint32_t event_loop(const KParams& P, Sim& S, RS& R, 
             TM_MARK(1);
             if (need) {
                 if (table_mode) {
-                    const int a = mlp_mode ? mlp_action<MB, kPre>(S, D.v, D.obs, Mp)
-                                           : table_action(S, D.v * NN + D.dst);
+                    int a = mlp_mode ? mlp_action<MB, kPre>(S, D.v, D.obs, Mp)
+                                     : table_action(S, D.v * NN + D.dst);
+                    if (EXPL) a = explore_action(S, H, P.explore_thr, D.d, D.v, a);
                     // (the row handoff: headline +2.1 % in A/B; config 4's MLP instance -2 %, so
                     // the MLP instances read the row again)
                     apply_decision<!RS::kMem && !MLP>(S, R, H, D.x, D.dst, D.start, D.uid, D.v, D.d, a, true,

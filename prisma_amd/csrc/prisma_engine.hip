@@ -108,10 +108,13 @@ __global__ void __launch_bounds__(64) prisma_reset_kernel_t(KParams P) {
 
 // step kernels (step_kernel.h): the table-policy instances with the --train / notify_dest
 // code paths are compiled here, the in-kernel DQN-buffer ones in prisma_engine_mlp.hip, the
-// ones without those paths in prisma_engine_lite.hip / prisma_engine_lite_mlp.hip
+// ones without those paths in prisma_engine_lite.hip / prisma_engine_lite_mlp.hip, the exploring
+// ones (prisma_run_explore) in prisma_engine_explore.hip / prisma_engine_explore_mlp.hip
 const void* prisma_pick_step_lite(int fs, int ls, bool tun);
 const void* prisma_pick_step_lite_mlp(int fs, int ls, bool tun);
 const void* prisma_pick_step_ctrl_mlp(int fs, int ls, bool tun);
+const void* prisma_pick_step_explore(int fs, int ls, bool tun);
+const void* prisma_pick_step_explore_mlp(int fs, int ls, bool tun);
 static const void* pick_step_ctrl(int fs, int ls, bool tun) { return pick_step<true, false>(fs, ls, tun); }
 
 template <int FS, int LS> const void* reset_kernel() { return (const void*)prisma_reset_kernel_t<FS, LS>; }
@@ -261,6 +264,8 @@ struct prisma_env {
     const void* k_step = nullptr;
     const void* k_step_mlp = nullptr;
     const void* k_reset = nullptr;
+    const void* k_explore = nullptr;     // exploring instances (prisma_run_explore): register engine
+    const void* k_explore_mlp = nullptr; // without the ctrl paths only
     float* d_mlp_rp = nullptr;           // interleaved DQN-buffer layers 2-4 (prisma_run, mode 4)
     unsigned char* d_spare = nullptr;    // next-episode images (register engine with auto_reset)
     uint32_t* d_rng = nullptr;           // ns-3 stream table (PRISMA_RNG_NS3, engine_layout.h kMrgPowers)
@@ -1053,6 +1058,10 @@ extern "C" int prisma_create(const prisma_topology_t* topo, const prisma_params_
         e->k_step = pick(L.FS, L.LS, L.tunnels != 0u);
         e->k_reset = pick_reset(L.FS, L.LS);
         e->k_step_mlp = pick_mlp(L.FS, L.LS, L.tunnels != 0u);
+        if (!ctrl) {
+            e->k_explore = prisma_pick_step_explore(L.FS, L.LS, L.tunnels != 0u);
+            e->k_explore_mlp = prisma_pick_step_explore_mlp(L.FS, L.LS, L.tunnels != 0u);
+        }
         e->kinfo.ctrl = ctrl ? 1u : 0u;
         e->kinfo.relay_ip = (L.tunnels && !ctrl) ? 1u : 0u;
         e->kinfo.relay_dec_bits = L.tunnels ? (ctrl ? 22u : kRipDecBits) : 0u;
@@ -1065,6 +1074,9 @@ extern "C" int prisma_create(const prisma_topology_t* topo, const prisma_params_
     (void)hipFuncSetAttribute(e->k_step_mlp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_mlp_bytes);
     (void)hipFuncSetAttribute(e->k_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bytes);
     (void)hipFuncSetAttribute(e->k_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bytes);
+    if (e->k_explore) (void)hipFuncSetAttribute(e->k_explore, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bytes);
+    if (e->k_explore_mlp)
+        (void)hipFuncSetAttribute(e->k_explore_mlp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_mlp_bytes);
     *out = e;
     return PRISMA_OK;
 }
@@ -1086,7 +1098,7 @@ static KParams base_params(prisma_env_t* e) {
 static int launch(prisma_env_t* e, const void* kern, KParams P, void* stream) {
     (void)hipSetDevice(e->device);
     void* args[] = { &P };
-    const size_t lds = kern == e->k_step_mlp ? e->lay.lds_mlp_bytes : e->lay.lds_bytes;
+    const size_t lds = (kern == e->k_step_mlp || kern == e->k_explore_mlp) ? e->lay.lds_mlp_bytes : e->lay.lds_bytes;
     hipError_t err = hipLaunchKernel(kern, dim3((unsigned)e->R), dim3(kWave), args, lds, (hipStream_t)stream);
     if (err == hipSuccess) err = hipGetLastError();
     if (err != hipSuccess) return set_err(PRISMA_ERR_LAUNCH, std::string("kernel launch failed: ") + hipGetErrorString(err));
@@ -1126,8 +1138,9 @@ extern "C" int prisma_step(prisma_env_t* e, const int32_t* actions, int32_t* obs
     return rc ? rc : auto_reset(e, stream);
 }
 
-extern "C" int prisma_run(prisma_env_t* e, int32_t policy, const void* policy_data, int32_t max_hops, void* stream) {
-    if (!e) return set_err(PRISMA_ERR_ARG, "null env");
+// prisma_run (explore_thr null) and prisma_run_explore
+static int run_fused(prisma_env_t* e, int32_t policy, const void* policy_data, int32_t max_hops,
+                     const uint32_t* explore_thr, void* stream) {
     if (!e->reset_done) return set_err(PRISMA_ERR_STATE, "prisma_reset must be called first");
     if ((policy != PRISMA_POLICY_TABLE && policy != PRISMA_POLICY_DQN_BUFFER) || !policy_data)
         return set_err(PRISMA_ERR_ARG, "policy must be PRISMA_POLICY_TABLE (uint8 table) or "
@@ -1154,12 +1167,35 @@ extern "C" int prisma_run(prisma_env_t* e, int32_t policy, const void* policy_da
         P.mlp_rp = e->d_mlp_rp;
     }
     P.max_hops = max_hops;
-    int rc = launch(e, P.mode == 4 ? e->k_step_mlp : e->k_step, P, stream);
+    P.explore_thr = explore_thr;
+    const void* kern = explore_thr ? (P.mode == 4 ? e->k_explore_mlp : e->k_explore)
+                                   : (P.mode == 4 ? e->k_step_mlp : e->k_step);
+    int rc = launch(e, kern, P, stream);
     // with auto_reset (register engine) the step kernel already continued every replica whose
     // episode ended into the next one; this launch refreshes the spare images it used, and
     // starts the next episode of the replicas it could not continue (memory engine; a second
     // episode end in one launch)
     return rc ? rc : auto_reset(e, stream);
+}
+
+extern "C" int prisma_run(prisma_env_t* e, int32_t policy, const void* policy_data, int32_t max_hops, void* stream) {
+    if (!e) return set_err(PRISMA_ERR_ARG, "null env");
+    return run_fused(e, policy, policy_data, max_hops, nullptr, stream);
+}
+
+extern "C" int prisma_run_explore(prisma_env_t* e, int32_t policy, const void* policy_data, int32_t max_hops,
+                                  const uint32_t* explore_thr, void* stream) {
+    if (!e) return set_err(PRISMA_ERR_ARG, "null env");
+    if (!explore_thr) return set_err(PRISMA_ERR_ARG, "explore_thr must be a device uint32 [n_nodes] array");
+    // exploration is compiled into instances of its own, which exist for the register-resident
+    // engine without the ctrl paths only
+    if (e->lay.mem)
+        return set_err(PRISMA_ERR_CONFIG, "prisma_run_explore: the memory-resident engine has no exploring instances");
+    if (e->kinfo.ctrl || !e->k_explore || !e->k_explore_mlp)
+        return set_err(PRISMA_ERR_CONFIG, "prisma_run_explore: this env runs the step kernels with the ctrl paths (train, "
+                                          "notify_dest, ns-3 streams, or a tunnelled overlay with log_capacity >= 2^18), "
+                                          "which have no exploring instances");
+    return run_fused(e, policy, policy_data, max_hops, explore_thr, stream);
 }
 
 extern "C" int prisma_read_counters(prisma_env_t* e, prisma_counters_t* host_out, void* stream) {

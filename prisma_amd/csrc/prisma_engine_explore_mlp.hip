@@ -1,0 +1,9 @@
+// prisma_engine_explore_mlp.hip -- the register-resident engine's step kernels with the
+// in-kernel DQN-buffer policy and epsilon-greedy exploration (engine_core.h explore_action),
+// without the --train echo / notify_dest code paths (step_kernel.h): prisma_run_explore with
+// PRISMA_POLICY_DQN_BUFFER.
+#include "step_kernel.h"
+
+const void* prisma_pick_step_explore_mlp(int fs, int ls, bool tun) { return pick_step<false, true, true>(fs, ls, tun); }
+
+PRISMA_TU_TIMING(prisma_debug_timing_explore_mlp)

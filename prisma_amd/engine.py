@@ -79,6 +79,7 @@ class _Plan(C.Structure):
 
 EXPORTS = [
     "prisma_abi_version", "prisma_last_error", "prisma_build_id", "prisma_create", "prisma_reset", "prisma_step", "prisma_run",
+    "prisma_run_explore",
     "prisma_read_counters", "prisma_counters_device", "prisma_log_view", "prisma_copy_log",
     "prisma_copy_counters", "prisma_gather_records", "prisma_state_bytes", "prisma_plan", "prisma_destroy",
     "prisma_compact_pending", "prisma_expand_actions", "prisma_kernel_info",
@@ -122,6 +123,8 @@ def load_library(path: str = None):
     L.prisma_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.prisma_run.restype = C.c_int
     L.prisma_run.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+    L.prisma_run_explore.restype = C.c_int
+    L.prisma_run_explore.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.prisma_read_counters.restype = C.c_int
     L.prisma_read_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.prisma_counters_device.restype = C.c_int
@@ -244,7 +247,8 @@ class PrismaEngine:
         else:
             fs, ls = ki["flow_slots"], ki["link_slots"]
             tun = "true" if ki["tunnels"] else "false"
-            # template arguments: slots, in-kernel MLP, tunnels, --train/notify_dest paths
+            # template arguments: slots, in-kernel MLP, tunnels, --train/notify_dest paths (the
+            # greedy instances; the sixth, EXPL, is true for the ones run(..., explore=) launches)
             self.kernel_name = f"prisma_step_kernel_t<{fs}, {ls}, false, {tun}, {ctrl}>"
             self.kernel_name_mlp = f"prisma_step_kernel_t<{fs}, {ls}, true, {tun}, {ctrl}>"
         self.obs = torch.zeros((self.R, self.W), dtype=torch.int32, device=self.torch_device)
@@ -327,11 +331,16 @@ class PrismaEngine:
                                           out.data_ptr(), _stream_handle(stream)))
         return out
 
-    def run(self, policy, max_hops: int, stream=None):
+    def run(self, policy, max_hops: int, stream=None, explore=None):
         """Fused in-kernel policy: every replica executes up to max_hops hops.
 
         policy: a device uint8 [N, N] action table (SP, DQ-routing argmin), or the device fp32
-        packed DQN-buffer weights of StackedQNet(kind="buffer").pack()."""
+        packed DQN-buffer weights of StackedQNet(kind="buffer").pack().
+
+        explore: None (greedy), or the epsilons of an epsilon-greedy rollout (prisma_run_explore;
+        prisma_amd/explore.py restates its draw rule): a scalar, or a float tensor / array
+        [n_nodes] indexed by underlay node id. Constant over the launch; a device tensor is
+        converted on the device without a host sync."""
         import torch
         n, d = self.topo.n_nodes, self.topo.max_deg
         if not policy.is_cuda:
@@ -343,7 +352,31 @@ class PrismaEngine:
         else:
             raise PrismaError("policy must be a uint8 [n_nodes, n_nodes] table or packed fp32 DQN-buffer weights")
         self._policy_keep = policy.contiguous()
-        _check(_lib.prisma_run(self.h, kind, self._policy_keep.data_ptr(), int(max_hops), _stream_handle(stream)))
+        if explore is None:
+            _check(_lib.prisma_run(self.h, kind, self._policy_keep.data_ptr(), int(max_hops), _stream_handle(stream)))
+            return
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
+            self._thr_keep = self._explore_thr(explore)
+        _check(_lib.prisma_run_explore(self.h, kind, self._policy_keep.data_ptr(), int(max_hops),
+                                       self._thr_keep.data_ptr(), _stream_handle(stream)))
+
+    def _explore_thr(self, explore):
+        """Epsilons -> the device thresholds of prisma_run_explore (explore.thresholds' rule:
+        floor(eps * 2^24 + 0.5) clamped to [0, 2^24]), in double precision as on the host.  A fresh
+        tensor per call: an earlier launch may still read the last one."""
+        import torch
+        n = self.topo.n_nodes
+        if torch.is_tensor(explore):
+            eps = explore.to(device=self.torch_device, dtype=torch.float64)
+        else:
+            eps = torch.from_numpy(np.asarray(explore, dtype=np.float64)).to(self.torch_device, non_blocking=True)
+        if eps.dim() == 0:
+            eps = eps.expand(n)
+        if eps.dim() != 1 or eps.numel() != n:
+            raise PrismaError("explore must be a scalar or one epsilon per node [n_nodes]")
+        thr = torch.floor(torch.nan_to_num(eps, nan=0.0) * float(1 << 24) + 0.5).clamp(0.0, float(1 << 24))
+        # (int32 storage: values <= 2^24, read as uint32 by the kernel)
+        return thr.to(torch.int32).contiguous()
 
     # -- outputs ----------------------------------------------------------
     def counters(self, stream=None) -> np.ndarray:

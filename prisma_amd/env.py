@@ -132,8 +132,9 @@ class VecRoutingEnv:
                 "now_ns": cf["now_ns"], "episode": cf["episode"]}
         return reward, done, info
 
-    def run(self, table: torch.Tensor, max_hops: int):
-        self.engine.run(table, max_hops)
+    def run(self, table: torch.Tensor, max_hops: int, explore=None):
+        """Fused launch (PrismaEngine.run); explore: epsilons of an epsilon-greedy rollout."""
+        self.engine.run(table, max_hops, explore=explore)
 
     def counters(self) -> np.ndarray:
         return self.engine.counters()

@@ -399,6 +399,13 @@ class QRoutingTrainer:
             a = torch.where(r < eps, ra, a)
         return a.to(torch.int32)
 
+    def explore_eps(self) -> torch.Tensor:
+        """Every node's epsilon now (device float64 [N], by underlay id): the LinearSchedule value
+        of its own transition count, 0 for nodes that decide nothing (no overlay neighbour) --
+        the ``explore`` argument of a fused rollout (train_fused)."""
+        eps = self.explore.value(self.transitions_seen)
+        return torch.where(self.deg > 0, eps, torch.zeros_like(eps))
+
     # -- one env step -----------------------------------------------------------
     def on_step(self, obs: torch.Tensor, info: dict):
         """Everything the Forwarder and Trainer threads do between two notifications: the
@@ -807,6 +814,48 @@ def train(env, trainer: QRoutingTrainer, steps: int, train_every: int = 1, sync_
         obs, _, _, info = env.step(a)
         trainer.on_step(obs, info)
         if s % train_every == 0:
+            per = trainer.train_step()
+            if per is not None:
+                losses.append(float(torch.nanmean(per)))
+    return losses
+
+
+def train_fused(env, trainer: QRoutingTrainer, launches: int, hops_per_launch: int, train_every: int = 1):
+    """Train from in-kernel rollouts: every launch is a fused epsilon-greedy run of up to
+    ``hops_per_launch`` hops per replica (VecRoutingEnv.run(..., explore=...), the exploring step
+    kernels) instead of one decision per replica per launch as in train().  Per launch: the fused
+    policy is refreshed from the online networks (argmin_table() for kind="routing", pack() for
+    "buffer"), the env runs with the nodes' current epsilons (explore_eps(): constant over the
+    launch, where the reference re-reads its schedule per decision), the replicas' clocks move to
+    the counters', the launch's completed transitions enter the buffers, the due syncs run, and
+    every ``train_every`` launches a training step.  Returns the mean losses of the training steps.
+
+    "ideal" signalling only (a transition enters the buffer when it completes; the others wait for
+    signalling packets the fused rollout does not hand out).  A launch that writes more records
+    than the env's log ring holds would lose transitions silently: RuntimeError; size
+    ``log_capacity`` above the decisions a launch makes (hops plus destination arrivals)."""
+    if trainer.signaling != "ideal":
+        raise ValueError("train_fused needs signaling_type='ideal' (hop transitions of 'NN' / 'target' wait for "
+                         "signalling packets): use train()")
+    if launches and int(hops_per_launch) < 1:
+        raise ValueError("hops_per_launch must be >= 1")
+    obs, info = env.reset()
+    trainer.advance_clock(info["now_ns"], info.get("episode"))
+    cap = env.engine.log_capacity
+    losses = []
+    for k in range(launches):
+        policy = trainer.q.argmin_table() if trainer.kind == "routing" else trainer.q.pack()
+        env.run(policy, hops_per_launch, explore=trainer.explore_eps())
+        cf = env._counter_fields()
+        over = int(((cf["dec_count"] - env._consumed) >= cap).sum().item())
+        if over:
+            raise RuntimeError(f"launch {k}: {over} replicas wrote at least log_capacity = {cap} records, so the "
+                               f"log no longer holds all of the launch's transitions: raise log_capacity or lower "
+                               f"hops_per_launch = {hops_per_launch}")
+        trainer.advance_clock(cf["now_ns"], cf["episode"])
+        trainer.observe(env.transitions())
+        trainer.check_sync()
+        if k % train_every == 0:
             per = trainer.train_step()
             if per is not None:
                 losses.append(float(torch.nanmean(per)))

@@ -1,0 +1,137 @@
+#!/usr/bin/env python
+"""Throughput of the training rollouts: the external path against the fused exploring kernels.
+
+4 096 Abilene replicas, DQ-routing agents, eps 0.1 at every node.  One JSON line per part:
+
+  a  trainer.train(): one decision per replica per launch (VecRoutingEnv.step, the torch policy,
+     gather_records and the counters every step) -- decisions/s and transitions/s into the buffers
+  b  trainer.train_fused(): one fused epsilon-greedy launch of --hops hops per replica, then the
+     launch's transitions into the buffers -- the same two figures
+  c  PrismaEngine.run(..., explore=0.1) alone against run() alone, hops/s (the cost of the draw)
+
+    python scripts/rollout_bench.py --part a        # or b, c; --repeat 2 prints each line twice
+
+Every part warms up first and is timed between device synchronisations.  bench.py stays the
+headline's yardstick; this script only compares the rollout paths with each other."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from prisma_amd import engine  # noqa: E402
+from prisma_amd.env import VecRoutingEnv  # noqa: E402
+from prisma_amd.trainer import QRoutingTrainer, train, train_fused  # noqa: E402
+
+
+def pow2_at_least(n: int) -> int:
+    p = 1024
+    while p < n:
+        p *= 2
+    return p
+
+
+def make(args, log_capacity):
+    env = VecRoutingEnv(args.topology, n_replicas=args.replicas, sim_time_s=60.0, auto_reset=1,
+                        log_capacity=log_capacity)
+    tr = QRoutingTrainer(env.topo, "routing", n_replicas=args.replicas, seed=0, batch_size=args.batch,
+                         eps_initial=args.eps, eps_final=args.eps)
+    return env, tr
+
+
+def wall(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, out
+
+
+def common(args, part):
+    return {"part": part, "topology": args.topology, "replicas": args.replicas, "agent": "dq_routing",
+            "eps": args.eps, "batch_size": args.batch, "build_id": engine.build_id(),
+            "device": torch.cuda.get_device_name(0)}
+
+
+def part_a(args):
+    env, tr = make(args, 8192)
+    train(env, tr, args.warmup_steps)
+    for _ in range(args.repeat):
+        seen0 = int(tr.buffers.total.sum())
+        dt, losses = wall(lambda: train(env, tr, args.steps))
+        out = common(args, "a")
+        out.update(path="train (external actions)", steps=args.steps, wall_s=round(dt, 4),
+                   decisions_per_s=round(args.replicas * args.steps / dt, 1),
+                   transitions_per_s=round((int(tr.buffers.total.sum()) - seen0) / dt, 1),
+                   train_steps=len(losses))
+        print(json.dumps(out), flush=True)
+    env.close()
+
+
+def part_b(args):
+    # a launch writes a record per hop and per destination arrival: twice the hops holds them
+    env, tr = make(args, pow2_at_least(2 * args.hops))
+    train_fused(env, tr, args.warmup_launches, args.hops)
+    for _ in range(args.repeat):
+        seen0 = int(tr.buffers.total.sum())
+        dt, losses = wall(lambda: train_fused(env, tr, args.launches, args.hops))
+        # (train_fused resets the env, and the hop totals restart with it: these are this call's)
+        hops = int(env.counters()["hops_total"].sum())
+        out = common(args, "b")
+        out.update(path="train_fused (in-kernel exploration)", launches=args.launches, hops_per_launch=args.hops,
+                   log_capacity=env.engine.log_capacity, wall_s=round(dt, 4),
+                   decisions_per_s=round(hops / dt, 1),
+                   transitions_per_s=round((int(tr.buffers.total.sum()) - seen0) / dt, 1),
+                   train_steps=len(losses))
+        print(json.dumps(out), flush=True)
+    env.close()
+
+
+def part_c(args):
+    env, tr = make(args, 8192)
+    table = tr.q.argmin_table()
+    eps = torch.full((env.topo.n_nodes,), args.eps, dtype=torch.float64, device=env.device)
+    for _ in range(args.repeat):
+        res = {}
+        for name, kw in (("greedy", {}), ("explore", {"explore": eps})):
+            env.engine.reset(0)
+            for _ in range(args.warmup_launches):
+                env.run(table, args.hops, **kw)
+            torch.cuda.synchronize()
+            h0 = int(env.counters()["hops_total"].sum())
+            dt, _ = wall(lambda: [env.run(table, args.hops, **kw) for _ in range(args.launches)])
+            cnt = env.counters()
+            assert int(cnt["error"].max()) == 0
+            res[name] = (int(cnt["hops_total"].sum()) - h0) / dt
+        out = common(args, "c")
+        out.update(path="run alone", launches=args.launches, hops_per_launch=args.hops,
+                   greedy_hops_per_s=round(res["greedy"], 1), explore_hops_per_s=round(res["explore"], 1),
+                   explore_over_greedy=round(res["explore"] / res["greedy"], 4))
+        print(json.dumps(out), flush=True)
+    env.close()
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("--part", choices=["a", "b", "c"], required=True)
+    p.add_argument("--topology", default="abilene")
+    p.add_argument("--replicas", type=int, default=4096)
+    p.add_argument("--eps", type=float, default=0.1)
+    p.add_argument("--batch", type=int, default=512)
+    p.add_argument("--hops", type=int, default=32768, help="hops per replica per fused launch (parts b, c)")
+    p.add_argument("--launches", type=int, default=3, help="timed fused launches (parts b, c)")
+    p.add_argument("--warmup-launches", type=int, default=1)
+    p.add_argument("--steps", type=int, default=200, help="timed env steps (part a)")
+    p.add_argument("--warmup-steps", type=int, default=20)
+    p.add_argument("--repeat", type=int, default=2, help="timed repeats, one JSON line each (the spread)")
+    args = p.parse_args(argv)
+    {"a": part_a, "b": part_b, "c": part_c}[args.part](args)
+
+
+if __name__ == "__main__":
+    main()
