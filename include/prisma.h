@@ -70,7 +70,8 @@ extern "C" {
                                       one-hot input is obs[0] (the overlay
                                       index of the destination)               */
 
-/* engine selection (prisma_params_t.engine) */
+/* engine selection (prisma_params_t.engine).  Either engine: overlay degree
+   <= 55 (obs_width <= 56; prisma_record_t), else PRISMA_ERR_CONFIG */
 #define PRISMA_ENGINE_AUTO     0   /* register-resident when the topology fits it */
 #define PRISMA_ENGINE_REGISTER 1   /* replica state in VGPRs + LDS: <= 255 nodes,
                                       256 links / tunnels / big-signalling
@@ -216,7 +217,9 @@ typedef struct prisma_params {
  * on the microsecond-formatted times (packet-manager.cc:127-128 ->
  * forwarder.py:208,360), bit-identical to the Python float.
  * Record size is 32 + 4 * obs_width bytes (obs_width = 1 + max_deg rounded up
- * to a multiple of 4, so records are whole 16-byte rows).
+ * to a multiple of 4, so records are whole 16-byte rows).  The engines write
+ * a record as one 64-lane store of its 8 header words and obs_width
+ * observation words, so obs_width <= 56: max_deg <= 55, record size <= 256.
  */
 typedef struct prisma_record {
     int64_t  t_ns;

@@ -602,7 +602,11 @@ static int build_layout(const prisma_topology_t* T, const prisma_params_t* P, La
     int rc = plan_overlay(T, OP);
     if (rc) return rc;
     if (OP.maxdeg != T->max_deg) return set_err(PRISMA_ERR_CONFIG, "max_deg mismatch (largest overlay degree)");
-    if (OP.maxdeg > 127) return set_err(PRISMA_ERR_CONFIG, "degree above 127");
+    // (both engines hold one observation word per lane and write a record as one wave store of
+    // its 8 header words + obs_width: 8 + ((1 + 55 + 3) & ~3) = 64 lanes is the most)
+    if (OP.maxdeg > 55)
+        return set_err(PRISMA_ERR_CONFIG, "overlay degree above 55: a record's 8 header words + obs_width "
+                                          "(1 + max_deg rounded up to 4) must fit one 64-lane store");
     for (int f = 0; f < F; ++f) {
         if (T->flow_src[f] < 0 || T->flow_src[f] >= N || T->flow_dst[f] < 0 || T->flow_dst[f] >= N ||
             T->flow_src[f] == T->flow_dst[f] || T->flow_rate_bps[f] == 0 ||

@@ -13,8 +13,9 @@ class SteppedOracle:
     """policy: ("table", uint8 [N, N]) or ("mlp", packed fp32).  thr: uint32 [N] by underlay id.
     base: global log index of this episode's first record (episodes after the first)."""
 
-    def __init__(self, oracle_mod, topo, params, replica, thr, policy, episode=0, base=0):
+    def __init__(self, oracle_mod, topo, params, replica, thr, policy, episode=0, base=0, scalar_check=True):
         self.O, self.topo, self.params = oracle_mod, topo, params
+        self.scalar_check = scalar_check                   # explore_action per decision beside the vectorised draw
         self.gid, self.episode, self.base = int(replica), int(episode), int(base)
         self.thr = np.asarray(thr, dtype=np.uint32)
         self.kind, self.pol = policy
@@ -43,11 +44,12 @@ class SteppedOracle:
             g = int(self.pol[v, int(self.topo.overlay_nodes[int(self.obs[0])])])
         else:
             g = self.o.mlp_action(self.pol, v, self.obs)
-        a = explore.explore_action(self.params["seed"], self.gid, self.base + k, self.episode,
-                                   int(self.thr[v]), deg, g)
-        c = self._draw(k)                                  # the vectorised draw says the same
+        c = self._draw(k)
         hit = (int(c[0]) >> 8) < int(self.thr[v])
-        assert a == (((int(c[1]) * deg) >> 32) if hit else g)
+        a = ((int(c[1]) * deg) >> 32) if hit else g
+        if self.scalar_check:                              # the scalar rule says the same as the vectorised draw
+            assert a == explore.explore_action(self.params["seed"], self.gid, self.base + k, self.episode,
+                                               int(self.thr[v]), deg, g)
         assert 0 <= a < deg or not hit
         self.decisions += 1
         self.explored += int(hit)

@@ -134,6 +134,58 @@ def check_near_ties(net_cpu, weights_host, checker, recs, rel_tol=1e-5):
     return len(dec), int((ak != at).sum()), float(dq), float(gap.max())
 
 
+def first_difference(got, ref):
+    """Index of the first record that differs byte for byte, or None."""
+    if got.tobytes() == ref.tobytes():
+        return None
+    return next((i for i in range(min(len(got), len(ref))) if got[i].tobytes() != ref[i].tobytes()),
+                min(len(got), len(ref)))
+
+
+def run_fused_both(oracle_mod, topo, params, R, H, policy, *, launches=1, kernel=None, net_cpu=None, label=""):
+    """R replicas x H hops of a fused policy, ("table", uint8 [N, N]) or ("mlp", packed fp32 numpy),
+    in `launches` launches on the engine and in one run on the oracle: every record and the
+    counters of every replica byte for byte, as test_gpu_parity.run_table_both.  kernel: the
+    prisma_kernel_info fields the engine must report.  net_cpu: the torch model of an MLP policy,
+    for check_near_ties.  Returns (counters, per-replica oracle records)."""
+    import torch
+    from prisma_amd.engine import PrismaEngine
+    kind, pol = policy
+    eng = PrismaEngine(topo, params, R)
+    try:
+        if kernel is not None:
+            ki = eng.kernel_info()
+            assert {k: ki[k] for k in kernel} == kernel, (label, ki)
+        eng.reset(0)
+        dev = torch.from_numpy(np.ascontiguousarray(pol)).cuda()
+        for _ in range(launches):
+            eng.run(dev, H // launches)
+        torch.cuda.synchronize()
+        cnt = eng.counters()
+        log = eng.log_tensor().cpu().numpy()
+        refs = []
+        for r in range(R):
+            o = oracle_mod.OracleSim(topo, params, replica=params["replica_base"] + r)
+            ran = o.run_table(pol, H) if kind == "table" else o.run_mlp(pol, H)
+            ref = o.records()
+            assert int(cnt[r]["error"]) == 0, (label, r, int(cnt[r]["error"]))
+            assert int(cnt[r]["hops_total"]) == ran, (label, r, int(cnt[r]["hops_total"]), ran)
+            assert int(cnt[r]["dec_count"]) == len(ref), (label, r, int(cnt[r]["dec_count"]), len(ref))
+            n = min(len(ref), eng.log_capacity)
+            got = eng.records(r, len(ref) - n, n, log_host=log)
+            bad = first_difference(got, ref[len(ref) - n:])
+            assert bad is None, (f"{label} replica {r}: record {len(ref) - n + bad} differs\n engine {got[bad]}\n "
+                                 f"oracle {ref[len(ref) - n + bad]}")
+            assert_counters_equal(cnt[r], o.counters(), r, f" ({label})")
+            if net_cpu is not None:
+                check_near_ties(net_cpu, pol, o, got)
+            refs.append(ref)
+            o.close()
+    finally:
+        eng.close()
+    return cnt, refs
+
+
 def compare_steady(oracle_mod, eng, topo, params, policy, *, t_target_s, hops_per_launch, min_episode=0,
                    replicas=None, net_cpu=None, max_launches=400, label="", log_tail=False):
     """Run `eng` launch by launch (fused policy) and compare every new decision record and the

@@ -162,6 +162,32 @@ def test_plan_sizes_and_limits_without_a_device():
         engine.plan(big, engine_params(big))
 
 
+def _star(d):
+    from prisma_amd.topology import Topology
+    adj = np.zeros((d + 1, d + 1), dtype=int)
+    adj[0, 1:] = adj[1:, 0] = 1
+    tm = np.zeros((d + 1, d + 1), dtype=object)
+    tm[1, 2] = tm[2, d] = 40000
+    return Topology.from_matrices(adj, tm)
+
+
+@pytest.mark.parametrize("eng", [engine.PRISMA_ENGINE_AUTO, engine.PRISMA_ENGINE_MEMORY], ids=["auto", "memory"])
+def test_plan_refuses_degrees_above_55(eng):
+    """Both engines write a record as one 64-lane store of 8 header words + obs_width (1 + max_deg
+    rounded up to 4) and hold one observation word per lane: degree 55 (obs_width 56, 256-B
+    records) is the widest either can deliver, and anything above is PRISMA_ERR_CONFIG."""
+    from prisma_amd.config import engine_params
+    t = _star(55)
+    p = engine.plan(t, engine_params(t, engine=eng))
+    assert p["obs_width"] == 56 and p["record_bytes"] == 256 and 8 + p["obs_width"] == 64
+    for d in (56, 63, 64, 85, 127):
+        t = _star(d)
+        # (prisma error -1: PRISMA_ERR_CONFIG)
+        with pytest.raises(engine.PrismaError, match=r"prisma error -1: overlay degree above 55.*64-lane store"):
+            engine.plan(t, engine_params(t, engine=eng))
+    assert re.search(r"#define\s+PRISMA_ERR_CONFIG\s+-1\b", open(HEADER).read())
+
+
 def test_plan_engine_selection():
     """Auto picks the register-resident engine when the topology fits it, the
     memory-resident one beyond (256 nodes, > 256 links); either can be forced
