@@ -106,7 +106,24 @@ extern "C" {
 #define PRISMA_ST_DESTINATION  3   /* packet reached its destination       */
 #define PRISMA_ST_DISCARDED    4   /* action >= degree: silently discarded  */
 
-/* runtime error bits (prisma_counters_t.error) */
+/* runtime error bits (prisma_counters_t.error)
+ *
+ * A failure is a defined return, not a fault.  The event that raises a bit ends the replica's
+ * episode there: error |= bit, episode_over = 1, and the launch's other replicas run on.
+ *  - LOGWRAP is raised by the arrival of a forwarded data packet (at its next overlay node, or
+ *    at a switch inside its tunnel) whose previous decision is log_capacity or more decisions
+ *    old.  That event consumes the packet and does nothing else: no record, no hop, no
+ *    forward, no counter but `events`.  dec_count is the index the refused record would have
+ *    had, so records [max(0, dec_count - log_capacity), dec_count) are all valid and unchanged.
+ *  - PINGIDX: the ping-back skips the acknowledgement; the packet is still forwarded or
+ *    received and counted like any other.
+ *  - now_ns is the time of the failing event; events counts every event up to and including
+ *    it; hops_total, dec_count and the other counters are those of the events before it.
+ *  - The bits are sticky until prisma_reset: later prisma_step / prisma_run calls execute
+ *    nothing for the replica and leave its counters and its log as they are.
+ *  - auto_reset leaves a failed replica alone: neither the in-launch restart nor the reset
+ *    after a launch starts its next episode.
+ */
 #define PRISMA_EBIT_RING       1u  /* link ring overflow                   */
 #define PRISMA_EBIT_WIRE       2u  /* more packets on a wire than sized    */
 #define PRISMA_EBIT_ACKORDER   4u  /* ping-back acknowledging a round more
@@ -168,8 +185,12 @@ typedef struct prisma_params {
     uint64_t seed;              /* simSeed                     [100]       */
     uint32_t replica_base;      /* global id of replica 0 (multi-GPU)      */
     uint32_t log_capacity;      /* records kept per replica (power of 2 in
-                                   [1024, 2^22]; must exceed the decisions
-                                   made while one packet crosses one link) */
+                                   [1024, 2^21]: queue entries keep 22 bits
+                                   of a decision's index, so every age up
+                                   to log_capacity stays distinguishable;
+                                   must exceed the decisions made while one
+                                   packet crosses one link: else
+                                   PRISMA_EBIT_LOGWRAP)                    */
     uint32_t notify_dest;       /* prisma_step also stops at arrivals at the
                                    destination (done=True notifications) and
                                    at control arrivals, obs [1000, a, b, c]:

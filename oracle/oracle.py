@@ -40,6 +40,7 @@ class OrConfig(C.Structure):
         ("tun_link", C.POINTER(C.c_int32)), ("next_link", C.POINTER(C.c_int32)),
         ("signaling_type", C.c_uint32), ("big_signaling", C.c_uint32), ("sync_step_s", C.c_float),
         ("big_signaling_bytes", C.c_uint32), ("rng_mode", C.c_uint32), ("rng_stream_offset", C.c_uint32),
+        ("log_capacity", C.c_uint32),
     ]
 
 
@@ -178,6 +179,7 @@ class OracleSim:
         cfg.big_signaling_bytes = int(params.get("big_signaling_bytes", 512))
         cfg.rng_mode = int(params.get("rng_mode", 0))
         cfg.rng_stream_offset = int(params.get("rng_stream_offset", 0))
+        cfg.log_capacity = int(params.get("log_capacity", 0))
         self._cfg = cfg
         self.W = topo.obs_width
         self.rec_dtype = record_dtype(self.W)

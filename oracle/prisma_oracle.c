@@ -835,6 +835,21 @@ static void finish_data_decision(or_sim_t* s, int action) {
     s->pend = 0;
 }
 
+/* The engine's decision log is a ring of log_capacity records, and a forwarded packet's uid,
+ * destination, start second and reward clock are read back from its previous decision's record
+ * (include/prisma.h PRISMA_EBIT_LOGWRAP).  Not part of the reference: the engine's defined
+ * failure, restated so that both sides stop at the same event.  A packet whose previous
+ * decision is log_capacity or more decisions old ends the episode with error bit 16; the
+ * event consumes the packet and does nothing else (no record, no forward, no counters). */
+static int log_wrapped(or_sim_t* s, const pkt_t* k) {
+    if (s->c.log_capacity == 0u) return 0;
+    const temp_t* tp = temp_of(s, k->uid);
+    if (!tp->active || s->rec_n - tp->dec < (int64_t)s->c.log_capacity) return 0;
+    s->cnt.error |= 16u;                                              /* PRISMA_EBIT_LOGWRAP */
+    s->over = 1;
+    return 1;
+}
+
 /* PointToPointNetDevice::Receive -> PacketRoutingEnv::NotifyPktRcv
  * (point-to-point-net-device.cc:371-467, packet-routing-gym.cc:231-267).
  * Order at the receiving switch v: MacRx trace (the overlay node's managers),
@@ -846,6 +861,8 @@ static int receive(or_sim_t* s, int di, int p) {
     pkt_t* k = &s->pk[p];
     const int overlay = s->c.overlay_index[v] >= 0;
     if (k->type == DATA_PACKET) {
+        /* a forwarded packet arriving at its next overlay node or at a switch inside its tunnel */
+        if (k->last_hop != 1000 && log_wrapped(s, k)) { pkt_free(s, p); return 0; }
         if (!(k->next_hop == v && k->valable)) {                      /* packet-manager.cc:115 */
             pkt_t orig = *k;
             if (k->next_hop != v) ip_forward(s, v, p);                /* inside a tunnel */

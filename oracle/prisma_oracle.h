@@ -69,6 +69,10 @@ typedef struct or_config {
        run; streams from rng_stream_offset on: the objects ns-3 itself creates first) */
     uint32_t rng_mode;
     uint32_t rng_stream_offset;
+    /* the engine's decision-log ring (prisma_params_t.log_capacity): the arrival of a forwarded
+       data packet whose previous decision is this many decisions old or more ends the episode
+       with error bit 16 (PRISMA_EBIT_LOGWRAP), as the engine does; 0: never */
+    uint32_t log_capacity;
 } or_config_t;
 
 typedef struct or_sim or_sim_t;

@@ -93,8 +93,9 @@ def engine_params(topo: Topology, *, sim_time_s: float = 60.0, seed: int = 100, 
     MRG32k3a RngStream streams, one per RandomVariable object in the reference's creation order,
     simSeed = seed + replica id; rng_stream_offset = the streams ns-3 creates before sim.cc's flow
     loop, include/prisma.h PRISMA_RNG_NS3)."""
-    if log_capacity < 1024 or log_capacity > (1 << 22) or log_capacity & (log_capacity - 1):
-        raise ValueError("log_capacity must be a power of two in [1024, 2^22]")
+    # (queue entries keep 22 bits of a decision's index: include/prisma.h prisma_params_t)
+    if log_capacity < 1024 or log_capacity > (1 << 21) or log_capacity & (log_capacity - 1):
+        raise ValueError("log_capacity must be a power of two in [1024, 2^21]")
     lp = _loss_penalty(max_buffer, packet_size, link_cap, topo.n_overlay) if loss_penalty is None else loss_penalty
     st = SIGNALING_TYPES.get(signaling_type, -1) if isinstance(signaling_type, str) else int(signaling_type)
     if st not in (0, 1, 2):

@@ -2045,7 +2045,8 @@ __device__ __forceinline__ int on_arrive(const Sim& S, RS& R, Hot& H, uint32_t l
         // (packet-manager.cc:115 -> not valid, no Notify) on the entry alone
         wire_pop(S, R, H, l, k);
         const uint32_t d = H.dec, dist = relay_dist(S, d, x);
-        if (dist >= L.log_cap()) fail(H, PRISMA_EBIT_LOGWRAP);
+        // (a failing event consumes its packet and does nothing else: include/prisma.h)
+        if (dist >= L.log_cap()) { fail(H, PRISMA_EBIT_LOGWRAP); return 0; }
         // IpForward decrements the TTL first and drops at 0 (no trace, no counter)
         const uint32_t tt = rip_ttl(x);
         if (tt == 1u) return 0;
@@ -2066,6 +2067,18 @@ __device__ __forceinline__ int on_arrive(const Sim& S, RS& R, Hot& H, uint32_t l
         // load and its consumption are unconditional on this path.)
         const uint32_t d = H.dec;
         const uint32_t dist = relay_dist(S, d, x);
+        // The previous decision is log_capacity or more decisions old: its record has been
+        // overwritten.  The event consumes the packet and does nothing else -- no record, no hop,
+        // no counter (include/prisma.h).  Here, ahead of the record's load: one site for every
+        // instance, and no tunnel is ever picked from an overwritten record.  (The exit costs
+        // the headline instance 1 to 2 % against setting the flag and executing the event, in
+        // alternating A/B, wherever on this path it stands: after the link update, at the
+        // record's first use, folded into the destination branch, or here.)
+        if (!(PRISMA_ABLATE & 1) && type == T_RELAY && __builtin_expect(dist >= L.log_cap(), 0)) {
+            wire_pop(S, R, H, l, k);
+            fail(H, PRISMA_EBIT_LOGWRAP);
+            return 0;
+        }
         const unsigned char* pr = S.logrep + (size_t)((d - dist) & (L.log_cap() - 1)) * L.rec_bytes();
         const uint4 ph = *(const uint4*)pr;
         const uint2 pw = *(const uint2*)(pr + 24);
@@ -2101,7 +2114,6 @@ __device__ __forceinline__ int on_arrive(const Sim& S, RS& R, Hot& H, uint32_t l
                 // (relay_ip: the entry named this node as the target, so the record is not this
                 // packet's -- the log wrapped past the 18-bit decision index)
                 if (relay_ip(S)) { fail(H, PRISMA_EBIT_LOGWRAP); return 0; }
-                if (dist >= L.log_cap()) fail(H, PRISMA_EBIT_LOGWRAP);
                 // IpForward decrements the TTL first and drops at 0 (no trace, no counter)
                 if (ttl_prev == (route(S, u, v) >> 8)) return 0;
                 if (!link_send(S, R, H, ti_link(route(S, v, ti_tgt(ti))), x))
@@ -2134,8 +2146,7 @@ __device__ __forceinline__ int on_arrive(const Sim& S, RS& R, Hot& H, uint32_t l
         } else if (PRISMA_ABLATE & 1) {
             dst = (x >> 2) & 255u; start = x >> 10; uid = 0; prev = (int32_t)d - 1;
         } else {
-            prev = (int32_t)(d - dist);
-            if (dist >= L.log_cap()) fail(H, PRISMA_EBIT_LOGWRAP);
+            prev = (int32_t)(d - dist);                             // (dist < log_cap: checked above)
             uid = uid_prev;
             dst = (w_prev >> 8) & 255u;
             start = w_prev >> 16;
@@ -2608,7 +2619,8 @@ __device__ __forceinline__ uint32_t event_loop(const KParams& P, Sim& S, RS& R, 
             if (EXPL) a = explore_action(S, H, P.explore_thr, u_ld32(&S.h->pend_dec), pn, a);
             H.hops_launch += finish_pending(S, R, H, a);
         } else if (P.actions) {
-            finish_pending(S, R, H, (int)rfl((uint32_t)P.actions[r]));
+            // (counted like a fused hop: hops_total is the hops since reset on every path)
+            H.hops_launch += finish_pending(S, R, H, (int)rfl((uint32_t)P.actions[r]));
         } else {
             H.stop = 1;                                // nothing to apply: re-emit the pending obs
         }
@@ -2727,7 +2739,9 @@ __device__ __forceinline__ uint32_t event_loop(const KParams& P, Sim& S, RS& R, 
         }
     }
 #endif
-    if (!H.error) lazy_resolve(S, R, H, false);      // elided completions up to where the launch stopped
+    // elided completions up to where the launch stopped -- after a failure too: the reference has
+    // executed them before the failing event, and `events` counts them (include/prisma.h)
+    lazy_resolve(S, R, H, false);
 
     hot_store(S, R, H);
     __syncthreads();

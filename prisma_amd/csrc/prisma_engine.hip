@@ -630,8 +630,10 @@ static int build_layout(const prisma_topology_t* T, const prisma_params_t* P, La
         return set_err(PRISMA_ERR_CONFIG, "bad link / ping parameters");
     if (!(P->sim_time_s > 0.0) || P->sim_time_s > 4095.0)
         return set_err(PRISMA_ERR_CONFIG, "sim_time_s must be in (0, 4095] (12-bit packet start second)");
-    if (P->log_capacity < 1024 || P->log_capacity > (1u << 22) || (P->log_capacity & (P->log_capacity - 1)))
-        return set_err(PRISMA_ERR_CONFIG, "log_capacity must be a power of two >= 1024");
+    // at most half the 22-bit decision index of a queue entry (kRelayMask): an age of log_capacity
+    // itself must stay representable for the PRISMA_EBIT_LOGWRAP check to see it
+    if (P->log_capacity < 1024 || P->log_capacity > (1u << 21) || (P->log_capacity & (P->log_capacity - 1)))
+        return set_err(PRISMA_ERR_CONFIG, "log_capacity must be a power of two in [1024, 2^21]");
     if (P->rng_mode > PRISMA_RNG_NS3) return set_err(PRISMA_ERR_CONFIG, "rng_mode must be PRISMA_RNG_PHILOX or _NS3");
     if (P->rng_mode == PRISMA_RNG_NS3 && (uint64_t)F >= (1ull << kMrgPowers))
         return set_err(PRISMA_ERR_CONFIG, "ns-3 streams: more than 2^18 flows");

@@ -101,8 +101,14 @@ class VecRoutingEnv:
                  arrivals never stop the engine and done is always False);
           info   dict: mask (uint8, 0 = the replica's episode ended this call), node (deciding node,
                  -1 if none), uid / prev (packet uid and the record index of its previous decision,
-                 -1 if fresh), control (bool), and "transitions": every replay transition completed
-                 since the previous step (transitions(): hop transitions and loss transitions).
+                 -1 if fresh), control (bool), error (int64 [R], the replica's PRISMA_EBIT_* bits,
+                 records.EBIT_*) and "transitions": every replay transition completed since the
+                 previous step (transitions(): hop transitions and loss transitions).
+
+        mask == 0 with error != 0 is a failure, not an episode end: the engine stopped the replica
+        at a defined failure (include/prisma.h, e.g. EBIT_LOGWRAP: log_capacity is too small for
+        the load), its records end there, and it stays stopped -- auto_reset included -- until
+        reset().
         """
         obs, mask, node = self.engine.step(actions.to(device=self.device, dtype=torch.int32))
         reward, done, info = self._info(obs, mask, node)
@@ -129,7 +135,9 @@ class VecRoutingEnv:
                 "prev": torch.where(has_prev, rec["prev"], torch.full_like(rec["prev"], -1)),
                 # the replica's clock at this notification (Agent.curr_time, forwarder.py:208) and
                 # its episode index: the trainer schedules syncs and signalling delays on them
-                "now_ns": cf["now_ns"], "episode": cf["episode"]}
+                "now_ns": cf["now_ns"], "episode": cf["episode"],
+                # PRISMA_EBIT_* bits: non-zero where mask == 0 means a failure, not an episode end
+                "error": cf["error"]}
         return reward, done, info
 
     def run(self, table: torch.Tensor, max_hops: int, explore=None):
@@ -140,7 +148,7 @@ class VecRoutingEnv:
         return self.engine.counters()
 
     def _counter_fields(self) -> dict:
-        """dec_count, now_ns and episode of every replica (device int64 [R])."""
+        """dec_count, now_ns, episode and error bits of every replica (device int64 [R])."""
         from .records import COUNTERS_DTYPE
         raw = self.engine.counters_tensor()                         # [R, 152] bytes
         w32 = raw.view(torch.int32)
@@ -148,7 +156,8 @@ class VecRoutingEnv:
         f = COUNTERS_DTYPE.fields
         return {"dec_count": w32[:, f["dec_count"][1] // 4].to(torch.int64) & 0xFFFFFFFF,
                 "now_ns": w64[:, f["now_ns"][1] // 8].clone(),
-                "episode": w32[:, f["episode"][1] // 4].to(torch.int64) & 0xFFFFFFFF}
+                "episode": w32[:, f["episode"][1] // 4].to(torch.int64) & 0xFFFFFFFF,
+                "error": w32[:, f["error"][1] // 4].to(torch.int64) & 0xFFFFFFFF}
 
     def _dec_counts(self) -> torch.Tensor:
         return self._counter_fields()["dec_count"]

@@ -6,6 +6,7 @@ import numpy as np
 ST_PENDING, ST_ENQUEUED, ST_DROPPED, ST_DESTINATION, ST_DISCARDED = 0, 1, 2, 3, 4
 
 EBIT_RING, EBIT_WIRE, EBIT_ACKORDER, EBIT_TIME, EBIT_LOGWRAP, EBIT_PINGIDX = 1, 2, 4, 8, 16, 32
+EBIT_NAMES = ("RING", "WIRE", "ACKORDER", "TIME", "LOGWRAP", "PINGIDX")      # bit b: 1 << b
 
 
 def record_dtype(obs_width: int) -> np.dtype:

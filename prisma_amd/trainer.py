@@ -100,6 +100,7 @@ import numpy as np
 import torch
 
 from .policies import StackedQNet
+from .records import EBIT_NAMES
 from .topology import Topology
 
 
@@ -833,7 +834,9 @@ def train_fused(env, trainer: QRoutingTrainer, launches: int, hops_per_launch: i
     "ideal" signalling only (a transition enters the buffer when it completes; the others wait for
     signalling packets the fused rollout does not hand out).  A launch that writes more records
     than the env's log ring holds would lose transitions silently: RuntimeError; size
-    ``log_capacity`` above the decisions a launch makes (hops plus destination arrivals)."""
+    ``log_capacity`` above the decisions a launch makes (hops plus destination arrivals).  A replica
+    the engine stopped on a PRISMA_EBIT_* failure produces nothing more: RuntimeError naming the
+    bits and the number of replicas."""
     if trainer.signaling != "ideal":
         raise ValueError("train_fused needs signaling_type='ideal' (hop transitions of 'NN' / 'target' wait for "
                          "signalling packets): use train()")
@@ -847,7 +850,17 @@ def train_fused(env, trainer: QRoutingTrainer, launches: int, hops_per_launch: i
         policy = trainer.q.argmin_table() if trainer.kind == "routing" else trainer.q.pack()
         env.run(policy, hops_per_launch, explore=trainer.explore_eps())
         cf = env._counter_fields()
-        over = int(((cf["dec_count"] - env._consumed) >= cap).sum().item())
+        # one host read: replicas over the log's size, and replicas per PRISMA_EBIT_* bit
+        over, *per_bit = torch.stack([((cf["dec_count"] - env._consumed) >= cap).sum()]
+                                     + [((cf["error"] >> b) & 1).sum() for b in range(len(EBIT_NAMES))]
+                                     + [(cf["error"] != 0).sum()]).tolist()
+        failed = per_bit.pop()
+        if failed:
+            bits = " | ".join(f"{name} ({1 << b})" for b, name in enumerate(EBIT_NAMES) if per_bit[b])
+            raise RuntimeError(f"launch {k}: {failed} of {env.R} replicas stopped on engine error bits {bits} "
+                               f"(include/prisma.h PRISMA_EBIT_*): their records end at the failure and they stay "
+                               f"stopped until reset()"
+                               + (f"; LOGWRAP: raise log_capacity = {cap}" if per_bit[EBIT_NAMES.index("LOGWRAP")] else ""))
         if over:
             raise RuntimeError(f"launch {k}: {over} replicas wrote at least log_capacity = {cap} records, so the "
                                f"log no longer holds all of the launch's transitions: raise log_capacity or lower "

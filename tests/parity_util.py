@@ -17,6 +17,86 @@ def assert_counters_equal(g, o, r, where=""):
     assert not bad, f"replica {r}{where}: counters differ {bad}"
 
 
+# ---- the log-wrap scenarios (tests/test_error_flags.py: the premises on the CPU;
+# tests/test_gpu_error_flags.py: the engine) -------------------------------------------------
+# Every scenario runs TM 0 with seed 100 for sim_time_s = 30 on replicas 5, 6 and 7.  At
+# log_capacity = WRAP_CAP the first record whose previous decision is WRAP_CAP or more records old
+# (d*, first_wrap) lies inside the run; at CLEAN_CAP no age of the same run reaches the capacity
+# (but on geant, clean = False); the controls never reach WRAP_CAP.  table: "sp" or the seed of
+# random_table.  hops: the oracle run the premises are computed over.
+WRAP_CAP, CLEAN_CAP, BIG_LOG = 1024, 2048, 65536
+WRAP_R, WRAP_BASE = 3, 5
+WRAP_MAX_HOPS = 8000                       # per replica on the GPU
+
+
+def _w(topo, lf, table, ping, hops, clean=True, seed=100, **params):
+    return dict(topo=topo, lf=lf, table=table, ping=ping, hops=hops, clean=clean, seed=seed, params=params)
+
+
+WRAP_SCENARIOS = {
+    "abilene_lf3": _w("abilene", 3.0, "sp", 0, 20000),
+    "abilene_lf3_train": _w("abilene", 3.0, "sp", 0, 20000, train=1),
+    "geant_lf2": _w("geant", 2.0, "sp", 1, 30000, clean=False),
+    "abilene_on_geant_lf3": _w("abilene_on_geant", 3.0, 11, 1, 30000),
+    # seed 129: on replicas 5 and 7 the check at a switch inside the tunnel fires first (found by a
+    # CPU search of seeds 100-139; under seed 100 the packet's arrival at the tunnel's end does)
+    "abilene_on_geant_lf3_s129": _w("abilene_on_geant", 3.0, 11, 1, 30000, seed=129),
+    # the same with --train (the ctrl instances' 22-bit entries): seed 130, replica 5, same search
+    "abilene_on_geant_lf3_s130_train": _w("abilene_on_geant", 3.0, 11, 1, 30000, seed=130, train=1),
+    "mesh3_lf20": _w("overlay_full_mesh_3n_abilene", 20.0, 11, 1, 30000),
+    "mesh3_lf20_train": _w("overlay_full_mesh_3n_abilene", 20.0, 11, 1, 30000, train=1),
+}
+WRAP_CONTROLS = {
+    "abilene_lf1": _w("abilene", 1.0, "sp", 0, 20000),
+    "abilene_on_geant_lf1": _w("abilene_on_geant", 1.0, "sp", 1, 30000),
+}
+
+
+def random_table(topo, seed):
+    rng = np.random.default_rng(seed)
+    table = np.zeros((topo.n_nodes, topo.n_nodes), dtype=np.uint8)
+    for u in topo.overlay_nodes:
+        table[u] = rng.integers(0, topo.degrees[u], topo.n_nodes)
+    return table
+
+
+def wrap_case(sc, log_capacity, **kw):
+    """(topology, engine params, action table) of a scenario at a log capacity."""
+    from prisma_amd.config import engine_params
+    from prisma_amd.topology import Topology, sp_next_hop_table
+    topo = Topology.example(sc["topo"], 0, sc["lf"])
+    args = dict(sim_time_s=30.0, seed=sc["seed"], ping_as_obs=sc["ping"], replica_base=WRAP_BASE,
+                log_capacity=log_capacity)
+    args.update(sc["params"])
+    args.update(kw)
+    table = sp_next_hop_table(topo) if sc["table"] == "sp" else random_table(topo, sc["table"])
+    return topo, engine_params(topo, **args), table
+
+
+WRAP_MLP_HOPS = 20000
+
+
+def wrap_mlp_case(log_capacity, **kw):
+    """The in-kernel DQN-buffer scenario: abilene at load factor 3.0 under StackedQNet(topo,
+    "buffer", seed=7), built on the CPU.  (topology, engine params, packed fp32 weights)."""
+    from prisma_amd.policies import StackedQNet
+    topo, params, _ = wrap_case(WRAP_SCENARIOS["abilene_lf3"], log_capacity, **kw)
+    return topo, params, StackedQNet(topo, "buffer", seed=7, device="cpu").pack().numpy()
+
+
+def record_ages(records):
+    """Per record, how many records back its packet's previous decision lies (0: a fresh packet)."""
+    prev = records["prev"].astype(np.int64)
+    return np.where(prev >= 0, np.arange(len(prev)) - prev, 0)
+
+
+def first_wrap(records, cap):
+    """Index of the first record whose previous decision is `cap` or more records old, or None:
+    the record a log of `cap` records can no longer build (PRISMA_EBIT_LOGWRAP)."""
+    hit = np.nonzero(record_ages(records) >= cap)[0]
+    return int(hit[0]) if len(hit) else None
+
+
 class OracleChain:
     """One replica's oracle, continued into the next episode when one ends (params.auto_reset),
     with decision indices numbered across episodes the way the engine's log numbers them (the log

@@ -88,17 +88,18 @@ def star(d, f, seed, rate=None):
     return Topology.from_matrices(adj, tm, name=f"star{d}")
 
 
-def tunnelled(n, m, k, f, seed, rate=None):
-    """A tree-plus-edges underlay as synth's with k overlay nodes (underlay leaves first) joined as an
-    overlay ring with one chord, f flows between overlay nodes.  The shallow tree keeps every
-    tunnel at 8 links or fewer (asserted)."""
+def tunnelled(n, m, k, f, seed, rate=None, inner=False):
+    """A tree-plus-edges underlay as synth's with k overlay nodes (underlay leaves first; inner:
+    inner underlay nodes first) joined as an overlay ring with one chord, f flows between overlay
+    nodes.  The shallow tree keeps every tunnel at 8 links or fewer (asserted)."""
     rng = np.random.default_rng([seed, n, m, f])
     adj = _tree_plus_edges(n, m, rng)
     # underlay leaves first: no tunnel crosses them, so few overlay nodes are ping bystanders (a
     # ping-back that crosses one of lower overlay degree can carry a tunnel index beyond it, which
-    # both engines and the oracle flag as PRISMA_EBIT_PINGIDX and end the episode on)
+    # both engines and the oracle flag as PRISMA_EBIT_PINGIDX and end the episode on).  inner: the
+    # opposite order, whose tunnels do cross overlay nodes (ERROR_CASES)
     order = rng.permutation(n)
-    on = np.sort(np.array(sorted(order, key=lambda v: adj[v].sum() > 1)[:k]))
+    on = np.sort(np.array(sorted(order, key=lambda v: (adj[v].sum() <= 1) if inner else (adj[v].sum() > 1))[:k]))
     mapo = np.full(n, -1, dtype=np.int64)
     mapo[on] = np.arange(k)
     oadj = np.zeros((k, k), dtype=np.int64)
@@ -167,6 +168,15 @@ STARS = {f"star{d}": _c("star", (d, min(64, d * (d - 1))), (1, _STAR_LS[d]), _ST
          for d in STAR_DEGREES}
 CASES = {**IDENTITY, **TUNNELLED, **STARS}
 
+# inner underlay nodes as overlay nodes: a ping-back crosses an overlay node of lower degree within
+# the first ping rounds, so every replica ends on PRISMA_EBIT_PINGIDX (tests/test_error_flags.py);
+# name: (builder arguments, builder seed, per-flow rate)
+ERROR_CASES = {
+    "inner_k9_s5": ((30, 40, 9, 60), 5, 30000),
+    "inner_k9_s6": ((30, 40, 9, 60), 6, 30000),
+    "inner_k8_s5": ((20, 26, 8, 40), 5, 30000),
+}
+
 # 513 flows: beyond the register engine (AUTO plans the memory engine, _REGISTER refuses)
 MEMORY_ONLY = (24, 23, 513)
 
@@ -188,6 +198,20 @@ def build(name):
     c = CASES[name]
     fn = {"synth": synth, "star": star, "tunnelled": tunnelled}[c["kind"]]
     return fn(*c["args"], SEED, c["rate"])
+
+
+@functools.lru_cache(maxsize=None)
+def build_error(name):
+    args, seed, rate = ERROR_CASES[name]
+    return tunnelled(*args, seed, rate, inner=True)
+
+
+def error_params(name, **kw):
+    """engine_params of an ERROR_CASES topology: the matrix's replicas, episode and log."""
+    from prisma_amd.config import engine_params
+    args = dict(sim_time_s=SIM_TIME_S, replica_base=REPLICA_BASE, log_capacity=LOG, seed=100 + ERROR_CASES[name][1])
+    args.update(kw)
+    return engine_params(build_error(name), **args)
 
 
 def case_params(name, **kw):

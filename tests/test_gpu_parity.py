@@ -418,7 +418,7 @@ def test_tunnel_ttl_expiry_parity(oracle_mod):
     run_table_both(oracle_mod, topo, params, 3, 10 ** 6, table)
 
 
-@pytest.mark.parametrize("log_bits,relay_ip", [(17, 1), (18, 0), (19, 0)])
+@pytest.mark.parametrize("log_bits,relay_ip", [(17, 1), (18, 0), (19, 0), (21, 0)])
 def test_tunnel_log_capacity_kernel_pick(log_bits, relay_ip):
     """The library's own report of the instance prisma_create picked (prisma_kernel_info): the
     relay-entry kernels keep 18 bits of the decision index (engine_layout.h rip_make), so their
