@@ -24,21 +24,6 @@ using namespace prisma;
 
 #define HIP_OK(x) ((x) == hipSuccess)
 
-// Diagnostic timing builds only (scripts/ablate.sh; results are NOT the
-// reference's): bit 0 skips the previous-record read (relay entries carry
-// dst/start), bit 1 skips the decision-record stores, bit 2 skips observe(), bit 3 draws from a
-// cheap hash instead of Philox, bit 4 takes a float log, bit 5 drops the reward's microsecond
-// formatting, bit 6 replaces the ping statistic by queued bytes (profiles/r06_ab/).
-#ifndef PRISMA_ABLATE
-#define PRISMA_ABLATE 0
-#endif
-#ifndef PRISMA_REWARD_LANES
-#define PRISMA_REWARD_LANES 1
-#endif
-
-
-// instruction-count experiments (A/B builds)
-
 // Diagnostic timing build (-DPRISMA_TIMING=1, scripts/timing.py): s_memtime
 // cycle totals per loop phase, summed over waves into g_prisma_timing.
 #ifndef PRISMA_TIMING
@@ -421,18 +406,13 @@ __device__ inline void sim_bind(Sim& S, const LV& L, unsigned char* lds, const u
 // 146-ms launch, the last ~22 ms with one wave left to hide its own latency.  Here a wave's priority
 // drops as its share of the launch's hops is done (3 below 5/8, 2 below 13/16, 1 below 15/16, then 0),
 // so a wave that is ahead yields issue to the ones behind it and the SIMD keeps all four to the end.
-#ifndef PRISMA_PRIO
-#define PRISMA_PRIO 1
-#endif
 // (round-6 A/B on one box, profiles/r06_ab/ab_prio.txt: thresholds 5/8, 13/16, 15/16 +13.4 % at
-// the headline and +8.9 % at config 3; 1/2, 3/4, 7/8 (PRISMA_PRIO=2) +13.2 %; 1/4, 1/2, 3/4 +10 %;
+// the headline and +8.9 % at config 3; 1/2, 3/4, 7/8 +13.2 %; 1/4, 1/2, 3/4 +10 %;
 // 7/8, 15/16, 31/32 +4.5 %; a least-progress-first rank over the SIMD's four waves, exchanged
 // through global memory every 64 or 256 hops, -2 %)
 __device__ __forceinline__ void prio_update(Sim& S, uint32_t hops_loop) {
     const uint32_t T = S.prio_total, p = S.prio_base + hops_loop;
-    uint32_t t1, t2, t3;
-    if (PRISMA_PRIO == 2) { t1 = T / 2; t2 = T - T / 4; t3 = T - T / 8; }
-    else { t1 = T / 2 + T / 8; t2 = T - T / 8 - T / 16; t3 = T - T / 16; }
+    const uint32_t t1 = T / 2 + T / 8, t2 = T - T / 8 - T / 16, t3 = T - T / 16;
     uint32_t next;
     if (p < t1) { __builtin_amdgcn_s_setprio(3); next = t1; }
     else if (p < t2) { __builtin_amdgcn_s_setprio(2); next = t2; }
@@ -808,13 +788,10 @@ __device__ __forceinline__ void transmit_start(const Sim& S, Hot& H, uint32_t l,
 // Whether a send must store its packet in the link's FIFO ring.  Tunnelled overlays and the
 // memory-resident engine keep the packets on a wire in wire slots (LDS / the link record), so a
 // packet that finds the transmitter idle and nothing queued goes straight onto the wire and its
-// ring slot is never read (PRISMA_RING_DIRECT): the store -- an HBM write there -- is skipped.  The
+// ring slot is never read: the store -- an HBM write there -- is skipped.  The
 // register-resident identity overlays read arrivals from the ring and always store.
-#ifndef PRISMA_RING_DIRECT
-#define PRISMA_RING_DIRECT 1
-#endif
 __device__ __forceinline__ bool ring_store_needed(const Sim& S, const LinkV& k) {
-    if (PRISMA_RING_DIRECT && (S.tun || S.mem)) return k.busy || k.n_queue != 0u;
+    if (S.tun || S.mem) return k.busy || k.n_queue != 0u;
     return true;
 }
 
@@ -967,7 +944,6 @@ __device__ __forceinline__ uint32_t ping_value_lane(double avg, uint32_t lo, dou
 template <int FS, int LS>
 __device__ __forceinline__ uint32_t observe_links(const Sim& S, const Regs<FS, LS>& R, const Hot& H, uint32_t v,
                                                   double now_s, int r0 = -1, int deg = 0) {
-    if (PRISMA_ABLATE & 4) return 0u;
     if (r0 < 0) { r0 = t_ovrow(S, v); deg = t_ovrow(S, v + 1) - r0; }
     const int lane = S.lane;
     uint32_t src = (uint32_t)(r0 + lane - 1);
@@ -980,7 +956,7 @@ __device__ __forceinline__ uint32_t observe_links(const Sim& S, const Regs<FS, L
 #pragma unroll
     for (int j = 0; j < LS; ++j) {
         uint32_t val;
-        if (pobs && !(PRISMA_ABLATE & 64))
+        if (pobs)
             val = ping_value_lane(ld_d(R.pav_lo.v[j], R.pav_hi.v[j]), R.pm_lo.v[j], ld_d(R.od_lo.v[j], R.od_hi.v[j]),
                                   H.ping_rounds, now_s);
         else
@@ -995,7 +971,6 @@ __device__ __forceinline__ uint32_t observe_links(const Sim& S, const Regs<FS, L
 __device__ __forceinline__ void write_record(const Sim& S, const Hot& H, uint32_t d, double reward, uint32_t uid,
                                              int32_t prev, uint32_t node, uint32_t dst, uint32_t start, int action,
                                              uint32_t status, uint32_t obs_reg, uint32_t ttl) {
-    if (PRISMA_ABLATE & 2) return;
     const int lane = S.lane;
     uint64_t rb = __double_as_longlong(reward);
     uint32_t w7 = (uint32_t)(uint8_t)(int8_t)action | (status << 8) | (ttl << 16) | ((H.episode & 0xffu) << 24);
@@ -1019,14 +994,12 @@ __device__ __forceinline__ void write_record(const Sim& S, const Hot& H, uint32_
 
 // action + status of a record written earlier (TTL and episode bytes kept)
 __device__ __forceinline__ void patch_record(const Sim& S, const Hot& H, uint32_t d, int action, uint32_t status) {
-    if (PRISMA_ABLATE & 2) return;
     if (S.lane == 0) {
         unsigned char* p = S.logrep + (size_t)(d & (S.lv.log_cap() - 1)) * S.lv.rec_bytes();
         *(uint16_t*)(p + 28) = (uint16_t)((uint32_t)(uint8_t)(int8_t)action | (status << 8));
     }
 }
 __device__ __forceinline__ void patch_status(const Sim& S, uint32_t d, uint32_t status) {
-    if (PRISMA_ABLATE & 2) return;
     if (S.lane == 0) S.logrep[(size_t)(d & (S.lv.log_cap() - 1)) * S.lv.rec_bytes() + 29] = (unsigned char)status;
 }
 
@@ -1139,8 +1112,7 @@ __device__ __forceinline__ void apply_decision(const Sim& S, RS& R, Hot& H, uint
         // (memory-resident engine without the ctrl paths: the destination instead of the
         // source, engine_layout.h)
         const uint32_t src = (RS::kMem && !S.ctrl) ? dst : ent_src(x, v);
-        const uint32_t fwd = relay_ip(S) ? rip_make(d, ttl, ti_tgt(tiw))
-                           : ((PRISMA_ABLATE & 1) ? (T_RELAY | (dst << 2) | (start << 10) | (src << 24)) : r_make(d, src));
+        const uint32_t fwd = relay_ip(S) ? rip_make(d, ttl, ti_tgt(tiw)) : r_make(d, src);
         TP2(7);
         if (link_send(S, R, H, l, fwd)) {                         // lastHop = v, previous decision = d
             status = PRISMA_ST_ENQUEUED;
@@ -1321,17 +1293,12 @@ __device__ __forceinline__ void flow_next(const Sim& S, RS& R, Hot& H, uint32_t 
     // ~80 scalar instructions per flow event moved off the headline's busiest unit.  The MLP
     // instances keep the scalar rounds with their keys hoisted out of the event loop.
     uint32_t k0 = S.lv.seed_lo(), k1 = S.gid;
-    if (PRISMA_ABLATE & 8) {                                      // diagnostic: a cheap hash, not Philox
-        c[0] = (f * 2654435761u) ^ (draw * 2246822519u) ^ (k1 * 3266489917u) ^ H.episode;
-        c[1] = c[0] * 668265263u ^ (c[0] >> 15);
-    } else {
     if (!S.mlp_inst) asm volatile("" : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]), "+v"(k0), "+v"(k1));
     philox4x32_10(c, k0, k1);
     if (!S.mlp_inst) { c[0] = __builtin_amdgcn_readfirstlane(c[0]); c[1] = __builtin_amdgcn_readfirstlane(c[1]); }
-    }
     uint64_t u53 = ((uint64_t)(c[0] >> 5) << 26) | (uint64_t)(c[1] >> 6);
     double U = ((double)u53 + 1.0) * (1.0 / 9007199254740992.0);
-    double delay = (PRISMA_ABLATE & 16) ? -t_fmean(S, f) * (double)__logf((float)U) : -t_fmean(S, f) * det_log(U);
+    double delay = -t_fmean(S, f) * det_log(U);
     int64_t t = H.now + sec_to_ns(delay);
     if constexpr (RS::kMem) TM_FLOW(2);
     flow_set(S, R, H, f, t, H.seq++, draw + 1);
@@ -1416,43 +1383,21 @@ __host__ __device__ constexpr int mlp_rp_node_floats(int D) {   // rounded to wh
     return (mlp_rp_l1_floats(D) + 2 * mlp_rp_layer_floats(64) + mlp_rp_layer_floats(D) + 3) & ~3;
 }
 
-// B: float4 weight loads in flight per lane (one L2 round trip per B chunks); 4 where the
-// kernel must fit 128 VGPRs (4 waves per SIMD), more where it has 256
-template <int B>
-__device__ __forceinline__ float mlp_dense64(const Sim& S, const float* __restrict__ Wl, int lane, int units) {
-    const float4* __restrict__ W4 = (const float4*)Wl;
-    const float4* __restrict__ hb = (const float4*)S.hbuf;
-    const float b = Wl[64 * units + lane];
-    float acc = 0.0f;
-#pragma unroll
-    for (int c0 = 0; c0 < 16; c0 += B) {
-        float4 w[B];
-#pragma unroll
-        for (int c = 0; c < B; ++c) w[c] = W4[(c0 + c) * units + lane];
-#pragma unroll
-        for (int c = 0; c < B; ++c) {
-            const float4 h = hb[c0 + c];
-            acc = __builtin_fmaf(h.x, w[c].x, acc);
-            acc = __builtin_fmaf(h.y, w[c].y, acc);
-            acc = __builtin_fmaf(h.z, w[c].z, acc);
-            acc = __builtin_fmaf(h.w, w[c].w, acc);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    return __fadd_rn(acc, b);
-}
-
-// B == kMlpAll (memory-resident engine, one wave per SIMD and VGPRs to spare): every
-// weight of layers 2-4 is loaded when the decision starts, one round trip in all
-constexpr int kMlpAll = 64;
+// memory-resident engine (one wave per SIMD and VGPRs to spare): every weight of layers 2-4
+// is loaded when the decision starts, one round trip in all
 struct MlpPre {
     float4 w2[16], w3[16], w4[16];
     float b2, b3, b4;
 };
 // what the memory-resident engine's arrival handler fetches for the decision that follows
-// (layer 1's buffer-branch chunks and bias, layer 2): it rides along the arrival's second
-// round trip, and layers 3-4 load while layers 1-2 compute
+// (layer 1's buffer-branch chunks and bias): it rides along the arrival's second
+// round trip; layer 2 is issued when the decision starts and layers 3-4 load while layers
+// 1-2 compute
 struct MlpPre1 {
+    // (w2, b2: layer 2's weights, which rode along too until round 5, never written or read now.
+    // They stay: the compiler scalarises this struct by its layout, and without them the
+    // memory-resident MLP kernels come out with another register allocation -- 143 SGPR spills
+    // for 116 in the ctrl instance)
     float4 w2[16];
     float b2;
     float4 wb[4];
@@ -1461,6 +1406,8 @@ struct MlpPre1 {
     bool has_w1;
 };
 
+// (l2: every caller loads layer 2.  The parameter and the pointer test stay: written without
+// them the memory-resident MLP kernels come out with another register allocation)
 __device__ __forceinline__ void mlp_preload(MlpPre& M, const float* __restrict__ RP, int lane, int D, int deg,
                                             bool l2 = true) {
     const float4* __restrict__ W2 = l2 ? (const float4*)RP : nullptr;
@@ -1498,31 +1445,22 @@ __device__ __forceinline__ void mlp_preload_w4(MlpPre& M, const float* __restric
     M.b4 = RP[2 * mlp_rp_layer_floats(64) + 64 * D + l4];
 }
 
-// layers 1-2 of a decision at node v (the one-hot row too when the destination dst is
+// layer 1 of a decision at node v (the one-hot row too when the destination dst is
 // known, has_w1): issued by the memory-resident engine's arrival handler together with
 // its second round trip (previous decision record, observation), so the decision finds
-// them in registers
-// PRISMA_PRE_W2: layer 2's weights ride along the arrival's second round trip (1) or are issued when
-// the decision starts (0, round 5: +4.8 % at config 5 -- the arrival's gather no longer waits behind
-// 17 weight loads, and their 64 VGPRs are not held across the arrival's tree repair)
-#ifndef PRISMA_PRE_W2
-#define PRISMA_PRE_W2 0
-#endif
+// it in registers
+// Layer 2's weights once rode along the arrival's second round trip too; they are issued when
+// the decision starts instead (round 5: +4.8 % at config 5 -- the arrival's gather no longer waits
+// behind 17 weight loads, and their 64 VGPRs are not held across the arrival's tree repair)
 __device__ __forceinline__ void mlp_preload_node(MlpPre1& M, const Sim& S, uint32_t v, uint32_t dst, bool has_w1) {
     const int lane = S.lane;
     v = rfl(v);                  // uniform: the row pointers come from scalar loads
     const int D = S.lv.max_deg();
     const float* __restrict__ RP1 = S.mlp_rp + (size_t)v * mlp_rp_node_floats(D);
-    const float* __restrict__ RP = RP1 + mlp_rp_l1_floats(D);
     const int deg = t_ovrow(S, v + 1) - t_ovrow(S, v);
     M.has_w1 = has_w1;
     M.w1v = 0.0f;
     if (has_w1 && lane < 32) M.w1v = S.mlp[((int)v * S.lv.N() + (int)dst) * 32 + (lane & 31)];
-    if (PRISMA_PRE_W2) {
-#pragma unroll
-        for (int c = 0; c < 16; ++c) M.w2[c] = ((const float4*)RP)[c * 64 + lane];
-        M.b2 = RP[64 * 64 + lane];
-    }
     const int j32 = lane & 31, nck = (deg + 3) >> 2;
     const float4* __restrict__ Wb4 = (const float4*)RP1;
 #pragma unroll
@@ -1547,11 +1485,9 @@ __device__ __forceinline__ float mlp_dense64_pre(const Sim& S, const float4 (&w)
 // Layers 2-4 of the register-resident instances with the weight loads one batch ahead: batch
 // t+1's loads (across layer boundaries too) are issued before batch t's FMAs, so each L2 round
 // trip overlaps a batch of FMAs instead of standing alone.  Per lane the same operations in
-// the same order as mlp_dense64 for each layer (bit-identical); layer 4's lanes past deg read
+// the same order as mlp_dense64_pre for each layer (bit-identical); layer 4's lanes past deg read
 // lane 0's weights and their outputs are discarded by the caller.
-#ifndef PRISMA_MLP_PIPE
-#define PRISMA_MLP_PIPE 1
-#endif
+// B: float4 weight loads in flight per lane and buffer (one L2 round trip per B chunks)
 template <int B>
 __device__ __forceinline__ void mlp_l2_first(float4 (&w0)[B], const float* __restrict__ RP, int lane) {
     const float4* __restrict__ W4 = (const float4*)RP;
@@ -1619,21 +1555,6 @@ __device__ __forceinline__ float mlp_l234_pipe(const Sim& S, const float* __rest
 // one-hot input: obs[0] (the destination's overlay index, lane 0 of obs_reg)
 __device__ __forceinline__ float rdlf(float x, uint32_t k) { return __uint_as_float(rdl(__float_as_uint(x), k)); }
 
-// x of lanes 1..n summed in lane order (((0 + x1) + x2) + ...), four readlanes issued per
-// step; a lane past n contributes -0.0f, the identity of round-to-nearest addition (the sum
-// starts at +0 and so is never -0), so the result equals the one-add-per-lane loop's
-__device__ __forceinline__ float lane_sum_ordered(float x, int n) {
-    float sum = 0.0f;
-    for (int k0 = 0; k0 < n; k0 += 4) {
-        float v[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = (k0 + i < n) ? rdlf(x, (uint32_t)(k0 + i + 1) & 63u) : -0.0f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) sum = __fadd_rn(sum, v[i]);
-    }
-    return sum;
-}
-
 // tf.argmin over q of lanes 0..n-1 as the reference's scan: the first minimum (learner.py:145)
 // (the register-resident instances: their degrees are small)
 __device__ __forceinline__ int lane_argmin_first_seq(float q, int n) {
@@ -1662,16 +1583,13 @@ __device__ __forceinline__ int lane_argmin_first(float q, int n) {
     return (int)__builtin_ctzll(__ballot(key == kmin));
 }
 
-// LayerNorm and layer 1 from LDS (the memory-resident engine, PRISMA_LN_LDS): the deg buffer
+// LayerNorm and layer 1 from LDS (the memory-resident engine): the deg buffer
 // values (and later their squared deviations and normalised values) sit at hbuf[0..deg-1], +0
 // past the degree, and every lane reads them back as 16-B broadcasts -- the sums and the layer-1
 // FMA chain run in the oracle's order on VGPR operands instead of a v_readlane per term.  A +0 term
 // is an exact identity here: the sums start at +0 and add non-negative values (never -0), and
 // fma(+0, w, acc) = acc for finite w and acc != -0 (acc starts at +0 and an exact cancellation
 // rounds to +0).
-#ifndef PRISMA_LN_LDS
-#define PRISMA_LN_LDS 1
-#endif
 __device__ __forceinline__ float lds_sum_ordered(const float4* hb4, int nck) {
     float4 h[8];
 #pragma unroll
@@ -1698,8 +1616,23 @@ __device__ __forceinline__ float div_deg(float a, float d, float rd) {
     return __builtin_fmaf(e, rd, q);
 }
 
-template <int B, bool PRE = false>
-__device__ __forceinline__ int mlp_action(const Sim& S, uint32_t v, uint32_t obs_reg, const MlpPre1& P1) {
+// mlp_action phase totals (timing build, scripts/timing.py)
+#if PRISMA_TIMING
+#define TM_MLP_START() uint64_t tq = TM_NOW(), tq1
+#define TM_MLP(i) do { tq1 = TM_NOW(); S.tmlp[i] += tq1 - tq; tq = tq1; } while (0)
+#else
+#define TM_MLP_START() do { } while (0)
+#define TM_MLP(i) do { } while (0)
+#endif
+
+// The DQN-buffer decision at node v, register-resident engine.
+// B: float4 weight loads in flight per lane (StepOcc::mlp_batch), as two half batches
+// (P1 is not used: this engine prefetches nothing on arrival.  The parameter stays, with the
+// object the pending-decision site constructs for it: without it the 24 register-resident MLP
+// kernels come out with another register allocation, as they do with `chunk` written out
+// in the layer-1 loop instead of as a closure)
+template <int B>
+__device__ __forceinline__ int mlp_action_reg(const Sim& S, uint32_t v, uint32_t obs_reg, const MlpPre1& P1) {
     const LV& L = S.lv;
     const int lane = S.lane;
     const int N = L.N(), D = L.max_deg();
@@ -1711,12 +1644,94 @@ __device__ __forceinline__ int mlp_action(const Sim& S, uint32_t v, uint32_t obs
     const float* __restrict__ W1 = S.mlp;
     const float* __restrict__ RP1 = S.mlp_rp + (size_t)v * mlp_rp_node_floats(D);
     const float* __restrict__ RP = RP1 + mlp_rp_l1_floats(D);
-#if PRISMA_TIMING
-    uint64_t tq = TM_NOW(), tq1;
-#define TM_MLP(i) do { tq1 = TM_NOW(); S.tmlp[i] += tq1 - tq; tq = tq1; } while (0)
-#else
-#define TM_MLP(i) do { } while (0)
-#endif
+    TM_MLP_START();
+    if (PRISMA_TP_SET == 0) TP_START();
+    TP0(0);
+    const int deg = t_ovrow(S, v + 1) - t_ovrow(S, v);
+    const uint32_t dst = rdl(obs_reg, 0);
+    // layer-1 weights first (independent of the normalisation): one W1 row element and
+    // b1 for the one-hot branch (lanes 0-31), the Wb chunks and bb for the buffers branch
+    // (lanes 32-63; deg <= D, so at most ceil(D/4) chunks)
+    const int j32 = lane & 31;
+    const int nck = (deg + 3) >> 2;
+    const float4* __restrict__ Wb4 = (const float4*)RP1;
+    const float w1v = (lane < 32) ? W1[((int)v * N + (int)dst) * 32 + j32] : 0.0f;
+    const float b1v = (lane < 32) ? RP1[128 * ((D + 3) / 4) + 32 + j32] : RP1[128 * ((D + 3) / 4) + j32];
+    float4 wb[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) wb[c] = (c < nck) ? Wb4[c * 32 + j32] : make_float4(0.f, 0.f, 0.f, 0.f);
+    // layer 2's first weights go out now and load during the LayerNorm and layer 1
+    constexpr int kPipeB = B >= 2 ? B / 2 : 1;
+    constexpr bool kPipeEarly = B >= 8;
+    float4 w20[kPipeB];
+    if constexpr (kPipeEarly) mlp_l2_first<kPipeB>(w20, RP, lane);
+    // LayerNormalization of the deg buffer values (population variance, epsilon 1e-3):
+    // lane k+1 holds buffer value k; sums run in k order through readlanes
+    // (the memory-resident engine's LDS form lost 0.5-1.2 % here at 4 waves per SIMD, round-5 A/B,
+    // its 4-wide sums and DPP argmin 1 %, A/B on GEANT)
+    const float xf = (float)obs_reg;
+    float sum = 0.0f;
+    for (int k = 0; k < deg; ++k) sum = __fadd_rn(sum, rdlf(xf, (uint32_t)(k + 1)));
+    TP0(1);
+    TP0(2);
+    const float mean = __fdiv_rn(sum, (float)deg);
+    const float dv = __fsub_rn(xf, mean);
+    const float sq = __fmul_rn(dv, dv);
+    float var = 0.0f;
+    for (int k = 0; k < deg; ++k) var = __fadd_rn(var, rdlf(sq, (uint32_t)(k + 1)));
+    TP0(3);
+    TP0(4);
+    var = __fdiv_rn(var, (float)deg);
+    const float den = __fsqrt_rn(__fadd_rn(var, 1e-3f));
+    const float xn = __fdiv_rn(dv, den);                          // lane k+1: normalised value k
+    TP0(5);
+    // layer 1: one-hot(dst) branch in lanes 0-31, buffers branch in lanes 32-63. The
+    // buffers dot product runs with every lane active (lanes 0-31 discard it): its
+    // readlanes read xn from lanes 1..deg, which must not sit in an inactive branch.
+    float acc = 0.0f;
+    auto chunk = [&](int c, const float4& w) {
+        const int k = 4 * c;
+        acc = __builtin_fmaf(rdlf(xn, (uint32_t)(k + 1)), w.x, acc);
+        if (k + 1 < deg) acc = __builtin_fmaf(rdlf(xn, (uint32_t)(k + 2)), w.y, acc);
+        if (k + 2 < deg) acc = __builtin_fmaf(rdlf(xn, (uint32_t)(k + 3)), w.z, acc);
+        if (k + 3 < deg) acc = __builtin_fmaf(rdlf(xn, (uint32_t)(k + 4)), w.w, acc);
+    };
+    for (int c = 0; c < nck; ++c) {
+        float4 w;
+        if (c < 4) {
+            w = (c == 0) ? wb[0] : (c == 1) ? wb[1] : (c == 2) ? wb[2] : wb[3];
+        } else {
+            w = Wb4[c * 32 + j32];
+        }
+        chunk(c, w);
+    }
+    TP0(6);
+    S.hbuf[lane] = det_elu(__fadd_rn(lane < 32 ? w1v : acc, b1v));
+    __builtin_amdgcn_wave_barrier();
+    TP0(7);
+    TM_MLP(0);
+    // (half batches double-buffered: the same weight registers as B loads in flight)
+    const float q4 = mlp_l234_pipe<kPipeB, kPipeEarly>(S, RP, lane, D, deg, w20);
+    __builtin_amdgcn_wave_barrier();
+    // tf.argmin: first minimum (learner.py:145)
+    return lane_argmin_first_seq(q4, deg);
+}
+
+// The DQN-buffer decision at node v, memory-resident engine (one wave per SIMD and VGPRs to
+// spare): every weight of layers 2-4 is loaded as the decision starts (MlpPre), one round trip
+// in all.  PRE: the decision follows an arrival that fetched P1 (mlp_preload_node); the pending
+// decision at launch start has none and loads everything here (P1 unused).
+template <bool PRE>
+__device__ __forceinline__ int mlp_action_mem(const Sim& S, uint32_t v, uint32_t obs_reg, const MlpPre1& P1) {
+    const LV& L = S.lv;
+    const int lane = S.lane;
+    const int N = L.N(), D = L.max_deg();
+    // v (and with it deg) uniform: see mlp_action_reg
+    v = rfl(v);
+    const float* __restrict__ W1 = S.mlp;
+    const float* __restrict__ RP1 = S.mlp_rp + (size_t)v * mlp_rp_node_floats(D);
+    const float* __restrict__ RP = RP1 + mlp_rp_l1_floats(D);
+    TM_MLP_START();
     if (PRISMA_TP_SET == 0) TP_START();
 #if PRISMA_TIMING
     if constexpr (PRE) __builtin_amdgcn_s_waitcnt(0);     // the arrival's loads (probe only)
@@ -1735,188 +1750,121 @@ __device__ __forceinline__ int mlp_action(const Sim& S, uint32_t v, uint32_t obs
     float w1v;
     if (PRE && P1.has_w1) w1v = P1.w1v;
     else w1v = (lane < 32) ? W1[((int)v * N + (int)dst) * 32 + j32] : 0.0f;
-    // memory-resident engine: buffer-branch chunks 4-7 (degrees 17-32) are loaded here, BEFORE
+    // buffer-branch chunks 4-7 (degrees 17-32) are loaded here, BEFORE
     // the layer 3-4 stream: the load counter is in order, so a chunk loaded inside layer 1
     // made layer 1 wait for the whole stream (and the compiler, unable to count the loop's
     // loads, waited for everything before layer 2)
+    // (always issued, chunk 0 again past the node's degree: no branch for the scheduler to
+    // hoist the stream's loads above)
     float4 wx[4];
-    if constexpr (B == kMlpAll) {
-        // (always issued, chunk 0 again past the node's degree: no branch for the scheduler to
-        // hoist the stream's loads above)
 #pragma unroll
-        for (int c = 0; c < 4; ++c) wx[c] = Wb4[((c + 4 < nck) ? c + 4 : 0) * 32 + j32];
-        __builtin_amdgcn_sched_barrier(0);
-    }
+    for (int c = 0; c < 4; ++c) wx[c] = Wb4[((c + 4 < nck) ? c + 4 : 0) * 32 + j32];
+    __builtin_amdgcn_sched_barrier(0);
     MlpPre M;
-    // PRE (memory-resident engine): layer 2 came with the arrival, and layers 3-4 are issued in
-    // two halves inside the LayerNorm below, so their issue overlaps its dependent chain instead
-    // of holding the wave in front of it
-    if constexpr (B == kMlpAll && !PRE) mlp_preload(M, RP, lane, D, deg, true);
-    if constexpr (B == kMlpAll && PRE && !PRISMA_PRE_W2) {
+    float b1v;
+    float4 wb[4];
+    if constexpr (PRE) {
+        // layer 2 is issued here, and layers 3-4 in two halves inside the LayerNorm below, so
+        // their issue overlaps its dependent chain instead of holding the wave in front of it
 #pragma unroll
         for (int c = 0; c < 16; ++c) M.w2[c] = ((const float4*)RP)[c * 64 + lane];
         M.b2 = RP[64 * 64 + lane];
         __builtin_amdgcn_sched_barrier(0);
-    }
-    float b1v;
-    float4 wb[4];
-    if constexpr (PRE) {
         b1v = P1.b1v;
 #pragma unroll
         for (int c = 0; c < 4; ++c) wb[c] = P1.wb[c];
     } else {
+        mlp_preload(M, RP, lane, D, deg);
         b1v = (lane < 32) ? RP1[128 * ((D + 3) / 4) + 32 + j32] : RP1[128 * ((D + 3) / 4) + j32];
 #pragma unroll
         for (int c = 0; c < 4; ++c) wb[c] = (c < nck) ? Wb4[c * 32 + j32] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    // register-resident instances (PRISMA_MLP_PIPE): layer 2's first weights go out now and
-    // load during the LayerNorm and layer 1
-    constexpr int kPipeB = (B != kMlpAll && B >= 2) ? B / 2 : 1;
-    constexpr bool kPipeEarly = B != kMlpAll && B >= 8;
-    float4 w20[kPipeB];
-    if constexpr (kPipeEarly && PRISMA_MLP_PIPE) mlp_l2_first<kPipeB>(w20, RP, lane);
-    // LayerNormalization of the deg buffer values (population variance, epsilon 1e-3):
-    // lane k+1 holds buffer value k; sums run in k order through readlanes
-    // (the memory-resident engine's single wave per SIMD gains from the 4-wide sums and the
-    // DPP argmin below; the register-resident MLP instances lost 1 % with them, A/B on GEANT)
+    // LayerNormalization of the deg buffer values (population variance, epsilon 1e-3) from
+    // LDS (lds_sum_ordered): lane k+1 holds buffer value k
     const float xf = (float)obs_reg;
-    // (the register-resident instances lost 0.5-1.2 % with it at 4 waves per SIMD, round-5 A/B)
-    constexpr bool kLnLds = (B == kMlpAll) && PRISMA_LN_LDS;
     const float4* hb4 = (const float4*)S.hbuf;
     const bool inb = lane >= 1 && lane <= deg;
     const float fdeg = (float)deg;
-    float rdeg = 0.0f;
-    float sum = 0.0f;
-    if constexpr (kLnLds) {
-        rdeg = __fdiv_rn(1.0f, fdeg);                               // off the sums' chain
-        S.hbuf[(lane - 1) & 63] = inb ? xf : 0.0f;                  // value k at hbuf[k]
-        __builtin_amdgcn_wave_barrier();
-        sum = lds_sum_ordered(hb4, nck);
-    } else if constexpr (B == kMlpAll) sum = lane_sum_ordered(xf, deg);
-    else for (int k = 0; k < deg; ++k) sum = __fadd_rn(sum, rdlf(xf, (uint32_t)(k + 1)));
+    const float rdeg = __fdiv_rn(1.0f, fdeg);                       // off the sums' chain
+    S.hbuf[(lane - 1) & 63] = inb ? xf : 0.0f;                      // value k at hbuf[k]
+    __builtin_amdgcn_wave_barrier();
+    const float sum = lds_sum_ordered(hb4, nck);
     TP0(1);
-    if constexpr (B == kMlpAll && PRE) {
+    if constexpr (PRE) {
         __builtin_amdgcn_sched_barrier(0);
         mlp_preload_w3(M, RP, lane);
         __builtin_amdgcn_sched_barrier(0);
     }
     TP0(2);
-    const float mean = kLnLds ? div_deg(sum, fdeg, rdeg) : __fdiv_rn(sum, (float)deg);
+    const float mean = div_deg(sum, fdeg, rdeg);
     const float dv = __fsub_rn(xf, mean);
     const float sq = __fmul_rn(dv, dv);
-    float var = 0.0f;
-    if constexpr (kLnLds) {
-        __builtin_amdgcn_wave_barrier();
-        S.hbuf[(lane - 1) & 63] = inb ? sq : 0.0f;
-        __builtin_amdgcn_wave_barrier();
-        var = lds_sum_ordered(hb4, nck);
-    } else if constexpr (B == kMlpAll) var = lane_sum_ordered(sq, deg);
-    else for (int k = 0; k < deg; ++k) var = __fadd_rn(var, rdlf(sq, (uint32_t)(k + 1)));
+    __builtin_amdgcn_wave_barrier();
+    S.hbuf[(lane - 1) & 63] = inb ? sq : 0.0f;
+    __builtin_amdgcn_wave_barrier();
+    float var = lds_sum_ordered(hb4, nck);
     TP0(3);
-    if constexpr (B == kMlpAll && PRE) {
+    if constexpr (PRE) {
         __builtin_amdgcn_sched_barrier(0);
         mlp_preload_w4(M, RP, lane, D, deg);
         __builtin_amdgcn_sched_barrier(0);
     }
     TP0(4);
-    var = kLnLds ? div_deg(var, fdeg, rdeg) : __fdiv_rn(var, (float)deg);
+    var = div_deg(var, fdeg, rdeg);
     const float den = __fsqrt_rn(__fadd_rn(var, 1e-3f));
     const float xn = __fdiv_rn(dv, den);                          // lane k+1: normalised value k
-    if constexpr (kLnLds) {
-        __builtin_amdgcn_wave_barrier();
-        S.hbuf[(lane - 1) & 63] = inb ? xn : 0.0f;
-        __builtin_amdgcn_wave_barrier();
-    }
+    __builtin_amdgcn_wave_barrier();
+    S.hbuf[(lane - 1) & 63] = inb ? xn : 0.0f;
+    __builtin_amdgcn_wave_barrier();
     TP0(5);
-    // layer 1: one-hot(dst) branch in lanes 0-31, buffers branch in lanes 32-63. The
-    // buffers dot product runs with every lane active (lanes 0-31 discard it): its
-    // readlanes read xn from lanes 1..deg, which must not sit in an inactive branch.
+    // layer 1: one-hot(dst) branch in lanes 0-31, buffers branch in lanes 32-63 (every lane
+    // computes the buffers dot product, lanes 0-31 discard it): every term of a chunk (+0 past
+    // the degree), the inputs as LDS broadcasts
     float acc = 0.0f;
-    auto chunk = [&](int c, const float4& w) {
-        const int k = 4 * c;
-        acc = __builtin_fmaf(rdlf(xn, (uint32_t)(k + 1)), w.x, acc);
-        if (k + 1 < deg) acc = __builtin_fmaf(rdlf(xn, (uint32_t)(k + 2)), w.y, acc);
-        if (k + 2 < deg) acc = __builtin_fmaf(rdlf(xn, (uint32_t)(k + 3)), w.z, acc);
-        if (k + 3 < deg) acc = __builtin_fmaf(rdlf(xn, (uint32_t)(k + 4)), w.w, acc);
+    auto chunk4 = [&](const float4& x, const float4& w) {
+        acc = __builtin_fmaf(x.x, w.x, acc);
+        acc = __builtin_fmaf(x.y, w.y, acc);
+        acc = __builtin_fmaf(x.z, w.z, acc);
+        acc = __builtin_fmaf(x.w, w.w, acc);
     };
-    if constexpr (kLnLds) {
-        // every term of a chunk (+0 past the degree), the inputs as LDS broadcasts
-        auto chunk4 = [&](const float4& x, const float4& w) {
-            acc = __builtin_fmaf(x.x, w.x, acc);
-            acc = __builtin_fmaf(x.y, w.y, acc);
-            acc = __builtin_fmaf(x.z, w.z, acc);
-            acc = __builtin_fmaf(x.w, w.w, acc);
-        };
-        float4 h[8];
+    float4 xh[8];
 #pragma unroll
-        for (int c = 0; c < 8; ++c) h[c] = hb4[c];
+    for (int c = 0; c < 8; ++c) xh[c] = hb4[c];
 #pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            if (c >= nck) break;
-            if constexpr (B == kMlpAll) chunk4(h[c], c < 4 ? wb[c & 3] : wx[c & 3]);
-            else chunk4(h[c], c < 4 ? wb[c & 3] : Wb4[c * 32 + j32]);
-        }
-        for (int c = 8; c < nck; ++c) chunk4(hb4[c], Wb4[c * 32 + j32]);
-    } else if constexpr (B == kMlpAll) {
+    for (int c = 0; c < 8; ++c) {
+        if (c >= nck) break;
         // chunks named at compile time (a runtime-indexed select over wb/wx put them on the stack)
-#pragma unroll
-        for (int c = 0; c < 8; ++c)
-            if (c < nck) chunk(c, c < 4 ? wb[c & 3] : wx[c & 3]);
-        for (int c = 8; c < nck; ++c) chunk(c, Wb4[c * 32 + j32]);
-    } else {
-        for (int c = 0; c < nck; ++c) {
-            float4 w;
-            if (c < 4) {
-                w = (c == 0) ? wb[0] : (c == 1) ? wb[1] : (c == 2) ? wb[2] : wb[3];
-            } else {
-                w = Wb4[c * 32 + j32];
-            }
-            chunk(c, w);
-        }
+        chunk4(xh[c], c < 4 ? wb[c & 3] : wx[c & 3]);
     }
+    for (int c = 8; c < nck; ++c) chunk4(hb4[c], Wb4[c * 32 + j32]);
     TP0(6);
-    float h = (B == kMlpAll) ? det_elu_sel(__fadd_rn(lane < 32 ? w1v : acc, b1v))
-                             : det_elu(__fadd_rn(lane < 32 ? w1v : acc, b1v));
-    if constexpr (kLnLds) __builtin_amdgcn_wave_barrier();
+    // (det_elu_sel, the ELU without branches: +1.7 % here; the register-resident instances keep
+    // det_elu)
+    float h = det_elu_sel(__fadd_rn(lane < 32 ? w1v : acc, b1v));
+    __builtin_amdgcn_wave_barrier();
     S.hbuf[lane] = h;
     __builtin_amdgcn_wave_barrier();
     TP0(7);
     TM_MLP(0);
-    if constexpr (B != kMlpAll && PRISMA_MLP_PIPE) {
-        // (half batches double-buffered: the same weight registers as B loads in flight)
-        const float q4 = mlp_l234_pipe<kPipeB, kPipeEarly>(S, RP, lane, D, deg, w20);
-        __builtin_amdgcn_wave_barrier();
-        return lane_argmin_first_seq(q4, deg);
-    }
-    if constexpr (PRE && PRISMA_PRE_W2) h = det_elu_sel(mlp_dense64_pre(S, P1.w2, P1.b2));
-    else if constexpr (PRE) h = det_elu_sel(mlp_dense64_pre(S, M.w2, M.b2));
-    else if constexpr (B == kMlpAll) h = det_elu_sel(mlp_dense64_pre(S, M.w2, M.b2));
-    else h = det_elu(mlp_dense64<B>(S, RP, lane, 64));
+    h = det_elu_sel(mlp_dense64_pre(S, M.w2, M.b2));
     __builtin_amdgcn_wave_barrier();
     S.hbuf[lane] = h;
     __builtin_amdgcn_wave_barrier();
     TP0(8);
     TM_MLP(1);
-    if constexpr (B == kMlpAll) h = det_elu_sel(mlp_dense64_pre(S, M.w3, M.b3));
-    else h = det_elu(mlp_dense64<B>(S, RP + mlp_rp_layer_floats(64), lane, 64));
+    h = det_elu_sel(mlp_dense64_pre(S, M.w3, M.b3));
     __builtin_amdgcn_wave_barrier();
     S.hbuf[lane] = h;
     __builtin_amdgcn_wave_barrier();
     TP0(9);
     TM_MLP(2);
-    float q = 0.0f;
-    if constexpr (B == kMlpAll) {
-        const float q4 = det_elu_sel(mlp_dense64_pre(S, M.w4, M.b4));
-        if (lane < deg) q = q4;
-    } else {
-        if (lane < deg) q = det_elu(mlp_dense64<B>(S, RP + 2 * mlp_rp_layer_floats(64), lane, D));
-    }
+    const float q4 = det_elu_sel(mlp_dense64_pre(S, M.w4, M.b4));
+    const float q = lane < deg ? q4 : 0.0f;
     __builtin_amdgcn_wave_barrier();
     TP0(10);
-    // tf.argmin: first minimum (learner.py:145)
-    int best;
-    if constexpr (B == kMlpAll) best = lane_argmin_first(q, deg);
-    else best = lane_argmin_first_seq(q, deg);
+    // tf.argmin: first minimum (learner.py:145), one DPP reduction (the register-resident
+    // instances lost 1 % with it)
+    const int best = lane_argmin_first(q, deg);
     TP0(11);
     TM_MLP(3);
     return best;
@@ -2074,7 +2022,7 @@ __device__ __forceinline__ int on_arrive(const Sim& S, RS& R, Hot& H, uint32_t l
         // the headline instance 1 to 2 % against setting the flag and executing the event, in
         // alternating A/B, wherever on this path it stands: after the link update, at the
         // record's first use, folded into the destination branch, or here.)
-        if (!(PRISMA_ABLATE & 1) && type == T_RELAY && __builtin_expect(dist >= L.log_cap(), 0)) {
+        if (type == T_RELAY &&__builtin_expect(dist >= L.log_cap(), 0)) {
             wire_pop(S, R, H, l, k);
             fail(H, PRISMA_EBIT_LOGWRAP);
             return 0;
@@ -2143,31 +2091,24 @@ __device__ __forceinline__ int on_arrive(const Sim& S, RS& R, Hot& H, uint32_t l
             start = s0 - ((s0 ^ f_parity(x)) & 1u);
             const uint32_t lu = H.uid - 1u;
             uid = lu - ((lu - f_uid(x)) & kUidMask);
-        } else if (PRISMA_ABLATE & 1) {
-            dst = (x >> 2) & 255u; start = x >> 10; uid = 0; prev = (int32_t)d - 1;
         } else {
             prev = (int32_t)(d - dist);                             // (dist < log_cap: checked above)
             uid = uid_prev;
             dst = (w_prev >> 8) & 255u;
             start = w_prev >> 16;
             last = w_prev & 255u;
-            if (PRISMA_ABLATE & 32) {
-                reward = (double)(uint32_t)(H.now - t_prev);                  // (diagnostic builds only)
-            } else if (PRISMA_REWARD_LANES) {
-                // the reward's two clock terms (forwarder.py:360) in lanes 0 and 1 of one vector
-                // evaluation -- now in even lanes, the previous decision's time in odd ones -- and
-                // lane 0 takes the difference with lane 1's term brought over by a DPP move
-                const uint32_t m = S.m1;                                      // -(lane & 1)
-                const int64_t tt = mk64((lo32(t_prev) & m) | (lo32(H.now) & ~m), (hi32(t_prev) & m) | (hi32(H.now) & ~m));
-                const double us = us_to_sec(py_micros(tt));
-                const uint64_t ub = (uint64_t)__double_as_longlong(us);
-                const double up = __longlong_as_double((long long)mk64(dpp_u32<0xB1, 0xF>((uint32_t)ub),
-                                                                       dpp_u32<0xB1, 0xF>((uint32_t)(ub >> 32))));
-                const uint64_t rb = (uint64_t)__double_as_longlong(us - up);
-                reward = __longlong_as_double((long long)mk64(rfl((uint32_t)rb), rfl((uint32_t)(rb >> 32))));
-            } else {
-                reward = us_to_sec(py_micros(H.now)) - us_to_sec(py_micros(t_prev));   // forwarder.py:360
-            }
+            // reward = us_to_sec(py_micros(now)) - us_to_sec(py_micros(t_prev)) (forwarder.py:360):
+            // the two clock terms in lanes 0 and 1 of one vector
+            // evaluation -- now in even lanes, the previous decision's time in odd ones -- and
+            // lane 0 takes the difference with lane 1's term brought over by a DPP move
+            const uint32_t m = S.m1;                                      // -(lane & 1)
+            const int64_t tt = mk64((lo32(t_prev) & m) | (lo32(H.now) & ~m), (hi32(t_prev) & m) | (hi32(H.now) & ~m));
+            const double us = us_to_sec(py_micros(tt));
+            const uint64_t ub = (uint64_t)__double_as_longlong(us);
+            const double up = __longlong_as_double((long long)mk64(dpp_u32<0xB1, 0xF>((uint32_t)ub),
+                                                                   dpp_u32<0xB1, 0xF>((uint32_t)(ub >> 32))));
+            const uint64_t rb = (uint64_t)__double_as_longlong(us - up);
+            reward = __longlong_as_double((long long)mk64(rfl((uint32_t)rb), rfl((uint32_t)(rb >> 32))));
             CNT_ADD(S, reward_sum, reward);
         }
         // obs[0] = m_map_overlay_array[dst] (the identity on identity overlays)
@@ -2590,6 +2531,7 @@ __device__ __forceinline__ bool spare_restart(const KParams&, Sim&, RS&, int, ui
 // needs an external action, or the end of the episode; publish the outputs.
 // ---------------------------------------------------------------------------
 // EXPL: the fused policy's action goes through explore_action at both decision sites
+// MB: mlp_action_reg's batch (the memory-resident engine passes 0)
 template <bool MLP, int MB, bool EXPL = false, class RS>
 __device__ __forceinline__ uint32_t event_loop(const KParams& P, Sim& S, RS& R, int r, uint32_t max_hops) {
     const int lane = S.lane;
@@ -2608,13 +2550,20 @@ __device__ __forceinline__ uint32_t event_loop(const KParams& P, Sim& S, RS& R, 
 
     H.stop = 0;
     H.hops_launch = 0;
-    if (PRISMA_PRIO && S.prio_total) prio_update(S, 0u);
+    if (S.prio_total) prio_update(S, 0u);
     if (H.pend && !H.over) {
         if (table_mode) {
             uint32_t pn = u_ld32(&S.h->pend_node), pd = u_ld32(&S.h->pend_ent[1]);
-            MlpPre1 M0;
-            int a = mlp_mode ? mlp_action<MB>(S, pn, (lane < L.W()) ? S.obs[lane] : 0u, M0)
-                             : table_action(S, pn * NN + pd);
+            int a;
+            if (!mlp_mode) {
+                a = table_action(S, pn * NN + pd);
+            } else if constexpr (RS::kMem) {
+                MlpPre1 M0;                              // (no arrival came before: nothing prefetched)
+                a = mlp_action_mem<false>(S, pn, (lane < L.W()) ? S.obs[lane] : 0u, M0);
+            } else {
+                MlpPre1 M0;                              // (never used: see mlp_action_reg)
+                a = mlp_action_reg<MB>(S, pn, (lane < L.W()) ? S.obs[lane] : 0u, M0);
+            }
             // (the instances without the ctrl paths: every pending notification is a data decision)
             if (EXPL) a = explore_action(S, H, P.explore_thr, u_ld32(&S.h->pend_dec), pn, a);
             H.hops_launch += finish_pending(S, R, H, a);
@@ -2681,8 +2630,10 @@ __device__ __forceinline__ uint32_t event_loop(const KParams& P, Sim& S, RS& R, 
             TM_MARK(1);
             if (need) {
                 if (table_mode) {
-                    int a = mlp_mode ? mlp_action<MB, kPre>(S, D.v, D.obs, Mp)
-                                     : table_action(S, D.v * NN + D.dst);
+                    int a;
+                    if (!mlp_mode) a = table_action(S, D.v * NN + D.dst);
+                    else if constexpr (RS::kMem) a = mlp_action_mem<true>(S, D.v, D.obs, Mp);
+                    else a = mlp_action_reg<MB>(S, D.v, D.obs, Mp);
                     if (EXPL) a = explore_action(S, H, P.explore_thr, D.d, D.v, a);
                     // (the row handoff: headline +2.1 % in A/B; config 4's MLP instance -2 %, so
                     // the MLP instances read the row again)
@@ -2692,7 +2643,7 @@ __device__ __forceinline__ uint32_t event_loop(const KParams& P, Sim& S, RS& R, 
                                    D.r0, D.deg);
                     H.hops_launch++;
                     if (H.hops_launch >= max_hops) H.stop = 1;
-                    if (PRISMA_PRIO && H.hops_launch == S.prio_next) prio_update(S, H.hops_launch);
+                    if (H.hops_launch == S.prio_next) prio_update(S, H.hops_launch);
                     TM_MARK(2);
                 } else {
                     if (lane == 0) {

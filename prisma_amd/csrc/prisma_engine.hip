@@ -291,9 +291,7 @@ extern "C" const char* prisma_last_error(void) { return g_err.c_str(); }
 
 static uint32_t align16(uint32_t x) { return (x + 15u) & ~15u; }
 // largest draw-cache group (build_layout; 2 or 3, engine_core.h flow_next; 1: no cache)
-#ifndef PRISMA_DCACHE_KMAX
-#define PRISMA_DCACHE_KMAX 3u
-#endif
+constexpr uint32_t kDcacheKmax = 3u;
 static uint32_t next_pow2(uint32_t x) { uint32_t p = 1; while (p < x) p <<= 1; return p; }
 
 // Overlay of a topology (host): tunnels, routing, control-packet load per link.
@@ -944,7 +942,7 @@ static int build_layout(const prisma_topology_t* T, const prisma_params_t* P, La
     L.s_dcache = 0u;
     if (!L.rng_mode && F > 0 && fs <= 2) {         // (the instances with its code: Regs::kDcache)
         const uint32_t t0 = per_cu(o + tb) == per_cu(o) ? tb : 0u;
-        for (uint32_t K = PRISMA_DCACHE_KMAX; K >= 2u; --K) {
+        for (uint32_t K = kDcacheKmax; K >= 2u; --K) {
             const uint32_t dc = align16(8u * (K - 1u) * (uint32_t)F);
             if (per_cu(o + dc + t0) == per_cu(o + t0)) { L.s_dcache = take(dc) | K; break; }
         }

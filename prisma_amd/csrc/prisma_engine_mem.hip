@@ -569,11 +569,8 @@ __global__ void __launch_bounds__(64) prisma_mem_step_kernel(KParams P) {
     S.mlp = P.mlp;
     S.mlp_rp = P.mlp_rp;
     S.ctrl = CTRL;
-#ifndef PRISMA_MLP_B_MEM
-#define PRISMA_MLP_B_MEM kMlpAll
-#endif
     top_load(S, R);
-    event_loop<MLP, PRISMA_MLP_B_MEM>(P, S, R, r, (uint32_t)P.max_hops);
+    event_loop<MLP, 0>(P, S, R, r, (uint32_t)P.max_hops);       // (MB = 0: the register engine's batch)
     top_store(S, R);
     __syncthreads();
     mem_stage(lds, P, r, lane, true);

@@ -9,18 +9,10 @@
 // VGPRs) for small replicas so 4096 of them are resident on 256 CUs at
 // once, 2 (<= 256) up to 512 flows x 128 links
 template <int FS, int LS> struct StepOcc {
-#ifdef PRISMA_DEV_WAVES
-    static constexpr int waves = PRISMA_DEV_WAVES;     // register-allocation experiments only
-#else
     static constexpr int waves = (FS <= 2 && LS == 1) ? 4 : (LS <= 2 ? 2 : 1);
-#endif
-#ifndef PRISMA_MLP_B_WIDE
-#define PRISMA_MLP_B_WIDE 8
-#endif
-#ifndef PRISMA_MLP_B_NARROW
-#define PRISMA_MLP_B_NARROW 4
-#endif
-    static constexpr int mlp_batch = waves >= 4 ? PRISMA_MLP_B_NARROW : PRISMA_MLP_B_WIDE;   // DQN-buffer loads in flight
+    // DQN-buffer weight loads in flight per lane: 4 where the kernel must fit 128 VGPRs
+    // (4 waves per SIMD), 8 where it has 256
+    static constexpr int mlp_batch = waves >= 4 ? 4 : 8;
 };
 
 // MLP: the in-kernel DQN-buffer policy is compiled in (mode 4 only); the table /

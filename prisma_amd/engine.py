@@ -91,7 +91,7 @@ _lib = None
 def load_library(path: str = None):
     """Load libprisma_amd.so and declare its C-ABI (raises if absent).
 
-    PRISMA_LIB overrides the path (diagnostic builds, e.g. scripts/ablate.sh).  The default
+    PRISMA_LIB overrides the path (diagnostic builds, e.g. scripts/build_variant.sh).  The default
     library must carry the build id of the sources beside it (prisma_amd/buildid.py): a stale
     binary raises instead of running."""
     global _lib

@@ -2,8 +2,7 @@
 # Build a diagnostic variant of the engine library with extra compiler flags into
 # prisma_amd/_ablate/libprisma_amd_<name>.so (all translation units, the product's flags).
 # Usage: bash scripts/build_variant.sh <name> [-DFLAG ...]; then on the GPU box
-# bash scripts/ab_libs.sh "<name> ..." <bench args>.  Results of -DPRISMA_ABLATE builds are
-# not parity results.  SRC_DIR=<dir> compiles the sources of another tree (e.g. a git archive of HEAD).
+# bash scripts/ab_libs.sh "<name> ..." <bench args>.  SRC_DIR=<dir> compiles the sources of another tree (e.g. a git archive of HEAD).
 set -e
 NAME=$1; shift
 O=/tmp/prisma_variant_$NAME
