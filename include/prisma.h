@@ -69,6 +69,22 @@ extern "C" {
                                       N = n_nodes, rows by underlay id; the
                                       one-hot input is obs[0] (the overlay
                                       index of the destination)               */
+/* The reduced DQN-buffer models: DQN_buffer_model's structure with both
+   first-layer branches B wide, NH hidden layers H wide and the deg outputs,
+   the same fixed fp32 operation order with 32 -> B and 64 -> H.  Packed fp32
+   weights, row-major, x @ W, N = n_nodes, D = max_deg, rows by underlay id:
+     W1[N][N][B] b1[N][B] Wb[N][D][B] bb[N][B] W2[N][2B][H] b2[N][H]
+     W3[N][H][H] b3[N][H]   (only when NH = 2)
+     Wo[N][H][D] bo[N][D]
+   Register-resident engine without the ctrl paths only (prisma_run below). */
+#define PRISMA_POLICY_DQN_LITE      3 /* DQN_buffer_lite_model (models.py:184-227):
+                                         B 16, H 32, NH 2                      */
+#define PRISMA_POLICY_DQN_LIGHTER   4 /* DQN_buffer_lighter_model (models.py:39-85):
+                                         B 16, H 32, NH 1                      */
+#define PRISMA_POLICY_DQN_LIGHTER_2 5 /* DQN_buffer_lighter_2_model (models.py:87-133):
+                                         B 8, H 16, NH 1                       */
+#define PRISMA_POLICY_DQN_LIGHTER_3 6 /* DQN_buffer_lighter_3_model (models.py:135-181):
+                                         B 4, H 8, NH 1                        */
 
 /* engine selection (prisma_params_t.engine).  Either engine: overlay degree
    <= 55 (obs_width <= 56; prisma_record_t), else PRISMA_ERR_CONFIG */
@@ -343,7 +359,15 @@ int prisma_step(prisma_env_t* env, const int32_t* actions, int32_t* obs_out,
  * (row-major, as StackedQNet.pack() lays them out; the library copies them
  * into an interleaved per-node layout on `stream` before each such launch,
  * so weights updated in place between calls take effect on the next call;
- * calls on one env are ordered by their streams: keep one stream per env).
+ * calls on one env are ordered by their streams: keep one stream per env),
+ * or PRISMA_POLICY_DQN_LITE, _DQN_LIGHTER, _DQN_LIGHTER_2, _DQN_LIGHTER_3 with
+ * the packed fp32 weights of that reduced model (the same repack per launch).
+ * The reduced models' kernels exist for the register-resident engine without
+ * the ctrl paths, as the exploring ones: an env whose prisma_kernel_info
+ * reports ctrl = 1 (train, notify_dest, PRISMA_RNG_NS3, a tunnelled overlay
+ * with log_capacity >= 2^18) or the memory-resident engine gets
+ * PRISMA_ERR_CONFIG for these ids (they were PRISMA_ERR_ARG before they
+ * existed; the ABI version is unchanged: no struct or signature moved).
  * A replica stops early at the end of its episode; with params.auto_reset
  * it starts the next episode before the call returns (one launch never
  * crosses an episode boundary). */

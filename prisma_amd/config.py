@@ -26,6 +26,12 @@ RNG_MODES = {"philox": 0, "ns3": 1}                           # include/prisma.h
 AGENT_TYPES = ["dqn_buffer", "dqn_routing", "dqn_buffer_fp", "dqn_buffer_lite", "dqn_buffer_lighter",
                "dqn_buffer_lighter_2", "dqn_buffer_lighter_3", "dqn_buffer_ff",
                "dqn_buffer_with_throughputs", "sp", "opt"]
+# the agent types with a network class here: agent_type -> StackedQNet kind (forwarder.py:52-69).
+# dqn_buffer_ff (another first layer), dqn_buffer_fp and dqn_buffer_with_throughputs (inputs the
+# engine does not produce) have none; sp and opt are tables.
+AGENT_MODEL_KINDS = {"dqn_buffer": "buffer", "dqn_routing": "routing", "dqn_buffer_lite": "buffer_lite",
+                     "dqn_buffer_lighter": "buffer_lighter", "dqn_buffer_lighter_2": "buffer_lighter_2",
+                     "dqn_buffer_lighter_3": "buffer_lighter_3"}
 
 
 def build_parser() -> argparse.ArgumentParser:

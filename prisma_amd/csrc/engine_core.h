@@ -105,6 +105,8 @@ struct KParams {
     const uint32_t* rng;         // ns-3 stream mode: the rng table (engine_layout.h kMrgPowers), or null
     const uint32_t* explore_thr; // [N] epsilon-greedy thresholds (prisma_run_explore, EXPL instances), or
                                  // null; last, so the other instances' kernarg offsets stay put
+    uint32_t lq_dims;            // reduced DQN-buffer models (the LQ instances): lq_pack_dims(B, H, NH) of the
+                                 // weights in `mlp` / `mlp_rp`, else 0; after explore_thr for the same reason
 };
 
 // ---------------------------------------------------------------------------
@@ -1717,6 +1719,217 @@ __device__ __forceinline__ int mlp_action_reg(const Sim& S, uint32_t v, uint32_t
     return lane_argmin_first_seq(q4, deg);
 }
 
+// ---- the reduced DQN-buffer models (models.py:39-227: DQN_buffer_lite / lighter / lighter_2 /
+// lighter_3; include/prisma.h PRISMA_POLICY_DQN_LITE ... _DQN_LIGHTER_3): DQN_buffer_model's
+// structure with both first-layer branches B wide, NH hidden layers H wide and the deg outputs,
+// B in {4, 8, 16}, H in {8, 16, 32}, NH in {1, 2}.  One instance set serves all of them: B, H and
+// NH are wave-uniform run-time values (KParams::lq_dims), so every pointer and loop bound below is
+// scalar.  The operation order is mlp_action_reg's with 32 -> B and 64 -> H: at
+// (32, 64, 2) it would be the oracle's.
+// The interleaved per-node copy (prisma_lightq_repack_kernel) is [L1][L2]([L3])[Lo]:
+// * L1: the buffers branch, chunk c holding Wb[4c..4c+3][j] as one float4 per unit j < B (rows
+//   k >= D zero), ceil(D / 4) chunks, then bb[B] and b1[B] (the one-hot rows of W1 stay in the
+//   caller's buffer: one row per decision);
+// * L2 (2B inputs, H units), L3 (H inputs, H units; NH = 2 only), Lo (H inputs, D units): chunk c
+//   holding W[4c..4c+3][j] as one float4 per unit j, then the bias row.
+// B and H are multiples of 4, so every section starts on a float4.
+__host__ __device__ constexpr uint32_t lq_pack_dims(int B, int H, int NH) {
+    return (uint32_t)B | ((uint32_t)H << 8) | ((uint32_t)NH << 16);
+}
+__host__ __device__ constexpr int lq_rp_l1_floats(int D, int B) { return 4 * B * ((D + 3) / 4) + 2 * B; }
+__host__ __device__ constexpr int lq_rp_layer_floats(int in, int units) { return in * units + units; }
+__host__ __device__ constexpr int lq_rp_node_floats(int D, int B, int H, int NH) {   // whole float4s
+    return (lq_rp_l1_floats(D, B) + lq_rp_layer_floats(2 * B, H) + (NH - 1) * lq_rp_layer_floats(H, H) +
+            lq_rp_layer_floats(H, D) + 3) & ~3;
+}
+
+// Layers 2.. of a reduced model as straight-line code, mlp_l234_pipe's shape: NH + 1 layers of NC
+// chunks each (the three widths have B / 2 = H / 4 = NC: 8, 4, 2, so the concat and the hidden
+// layers are equally deep and H = 4 NC), in batches of min(PB, NC) chunks through a ring of DEPTH
+// weight buffers: batch t + DEPTH - 1's loads (across layer boundaries too) are issued before
+// batch t's FMAs.  The 256-VGPR instances run 2 chunks x 3 buffers (four chunks ahead of the
+// chain in 24 weight registers; 4 x 2, mlp_l234_pipe's, left the (8, 2) instance 3 VGPR spills),
+// the 128-VGPR ones 1 chunk x 2 (8 registers; with 2 x 2 the (2, 1) instances spilled 9 and 12
+// VGPRs, with 1 x 3 one to four, with 1 x 2 none).  NC and NH are
+// template arguments so that every load, wait and FMA sits at a fixed place with no branch
+// between them; lightq_action_reg picks the copy by the wave-uniform widths.  Per lane the same
+// operations in the same order for each unit; the output layer's lanes past deg read lane 0's
+// weights, the hidden layers' lanes past H likewise, and their results are never read.
+// w0: layer 2's first half batch, issued by the caller before layer 1 when EARLY.
+template <int PB, int DEPTH, int NC, int NH, bool EARLY>
+__device__ __forceinline__ float lq_stream(const Sim& S, const float* __restrict__ RP, int lane, int D, int deg,
+                                           const float4 (&w0)[PB]) {
+    constexpr int H = 4 * NC, PBE = PB < NC ? PB : NC, NB = NC / PBE, T = (NH + 1) * NB;
+    constexpr int kLayer = lq_rp_layer_floats(H, H);    // = lq_rp_layer_floats(2 B, H): 2 B = H
+    static_assert(NC % PBE == 0 && DEPTH >= 2 && DEPTH - 1 <= T, "lq_stream: the batch must divide a layer's chunks");
+    const float4* __restrict__ hb = (const float4*)S.hbuf;
+    const int lH = lane < H ? lane : 0, lo = lane < deg ? lane : 0;
+    float4 w[DEPTH][PBE];
+    float bias[NH + 1];
+    if constexpr (EARLY) {
+#pragma unroll
+        for (int c = 0; c < PBE; ++c) w[0][c] = w0[c];
+        if constexpr (NB == 1) bias[0] = RP[H * H + lH];
+    }
+    auto issue = [&](int t) {
+        const int Lk = t / NB, c0 = (t % NB) * PBE;
+        const bool out = Lk == NH;
+        const int U = out ? D : H, ln = out ? lo : lH;
+        const float* __restrict__ Wl = RP + Lk * kLayer;
+        const float4* __restrict__ W4 = (const float4*)Wl;
+#pragma unroll
+        for (int c = 0; c < PBE; ++c) w[t % DEPTH][c] = W4[(c0 + c) * U + ln];
+        if (t % NB == NB - 1) bias[Lk] = Wl[H * U + ln];
+    };
+    float acc = 0.0f, q = 0.0f;
+    if constexpr (!EARLY) issue(0);
+#pragma unroll
+    for (int t = 1; t < DEPTH - 1; ++t) issue(t);
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        if (t + DEPTH - 1 < T) issue(t + DEPTH - 1);
+        __builtin_amdgcn_sched_barrier(0);
+        const int c0 = (t % NB) * PBE;
+#pragma unroll
+        for (int c = 0; c < PBE; ++c) {
+            const float4 h = hb[c0 + c];
+            acc = __builtin_fmaf(h.x, w[t % DEPTH][c].x, acc);
+            acc = __builtin_fmaf(h.y, w[t % DEPTH][c].y, acc);
+            acc = __builtin_fmaf(h.z, w[t % DEPTH][c].z, acc);
+            acc = __builtin_fmaf(h.w, w[t % DEPTH][c].w, acc);
+        }
+        if (t % NB == NB - 1) {
+            const int Lk = t / NB;
+            const float o = det_elu(__fadd_rn(acc, bias[Lk]));
+            acc = 0.0f;
+            if (Lk < NH) {
+                __builtin_amdgcn_wave_barrier();
+                S.hbuf[lane] = o;
+                __builtin_amdgcn_wave_barrier();
+            } else {
+                q = o;
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    return q;
+}
+
+// The reduced models' decision at node v, register-resident engine.
+// MB: float4 weight loads in flight per lane (StepOcc::mlp_batch), as in mlp_action_reg: layer 1
+// holds 4 Wb chunks; the layers after it stream as half batches of MB / 2 chunks (lq_stream).
+// Every weight load is unconditional: a lane past a layer's width reads lane 0's column and its
+// result is never read (hbuf slots past the width; outputs past deg), and a Wb chunk past the
+// node's degree reads chunk 0, so no load sits under an exec mask and the in-order load counter
+// can be waited on exactly.  Activations go through the 64 floats of S.hbuf (the 256 B every MLP
+// launch reserves): a layer is at most 32 wide here.
+template <int MB>
+__device__ __forceinline__ int lightq_action_reg(const Sim& S, uint32_t v, uint32_t obs_reg, uint32_t dims) {
+    const LV& L = S.lv;
+    // the lane id opaque here: every copy of the layer stream derives its own per-lane offsets
+    // from it (lane < H ? lane : 0, ...), which are invariants of the event loop -- hoisted out of
+    // it they sat in VGPRs across the whole loop (61 VGPR spills on the 4-wave instances)
+    int lane = S.lane;
+    asm volatile("" : "+v"(lane));
+    const int N = L.N(), D = L.max_deg();
+    // v, deg and the widths uniform: the row pointers come from scalar loads (see mlp_action_reg)
+    v = rfl(v);
+    dims = rfl(dims);
+    const int B = (int)(dims & 0xffu), H = (int)((dims >> 8) & 0xffu), NH = (int)(dims >> 16);
+    const float* __restrict__ W1 = S.mlp;
+    const float* __restrict__ RP1 = S.mlp_rp + (size_t)v * lq_rp_node_floats(D, B, H, NH);
+    const float* __restrict__ RP = RP1 + lq_rp_l1_floats(D, B);
+    const int deg = t_ovrow(S, v + 1) - t_ovrow(S, v);
+    const uint32_t dst = rdl(obs_reg, 0);
+    // layer 1: one-hot branch in lanes 0..B-1, buffers branch in lanes B..2B-1 (unit lane & (B-1));
+    // the lanes past 2B repeat them and write hbuf slots no layer reads
+    const int jb = lane & (B - 1);
+    const int nck = (deg + 3) >> 2;
+    const int kc = (D + 3) >> 2;
+    const float4* __restrict__ Wb4 = (const float4*)RP1;
+    const float w1v = W1[((int)v * N + (int)dst) * B + jb];
+    const float b1v = RP1[4 * B * kc + (lane < B ? B + jb : jb)];
+    float4 wb[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) wb[c] = Wb4[(c < nck ? c : 0) * B + jb];
+    // layer 2's first weights go out now and load during the LayerNorm and layer 1 (as
+    // mlp_action_reg: the 256-VGPR instances only); a chunk past the layer's reads chunk 0, unused
+    // chunks per batch x ring of buffers: 2 x 3 with 256 VGPRs, 1 x 2 with 128 (register figures of
+    // the alternatives: lq_stream)
+    constexpr int PB = MB >= 8 ? 2 : 1, kDepth = MB >= 8 ? 3 : 2;
+    constexpr bool kEarly = MB >= 8;
+    float4 w20[PB];
+    if constexpr (kEarly) {
+        const float4* __restrict__ W24 = (const float4*)RP;
+        const int lH = lane < H ? lane : 0, nc = H >> 2;
+#pragma unroll
+        for (int c = 0; c < PB; ++c) w20[c] = W24[(c < nc ? c : 0) * H + lH];
+    }
+
+    // LayerNormalization of the deg buffer values, mlp_action_reg's order
+    const float xf = (float)obs_reg;
+    float sum = 0.0f;
+    for (int k = 0; k < deg; ++k) sum = __fadd_rn(sum, rdlf(xf, (uint32_t)(k + 1)));
+    const float mean = __fdiv_rn(sum, (float)deg);
+    const float dv = __fsub_rn(xf, mean);
+    const float sq = __fmul_rn(dv, dv);
+    float var = 0.0f;
+    for (int k = 0; k < deg; ++k) var = __fadd_rn(var, rdlf(sq, (uint32_t)(k + 1)));
+    var = __fdiv_rn(var, (float)deg);
+    const float den = __fsqrt_rn(__fadd_rn(var, 1e-3f));
+    const float xn = __fdiv_rn(dv, den);                          // lane k+1: normalised value k
+    // the buffers dot product with every lane active (its readlanes read lanes 1..deg)
+    float acc = 0.0f;
+    auto chunk = [&](int c, const float4& w) {
+        const int k = 4 * c;
+        acc = __builtin_fmaf(rdlf(xn, (uint32_t)(k + 1)), w.x, acc);
+        if (k + 1 < deg) acc = __builtin_fmaf(rdlf(xn, (uint32_t)(k + 2)), w.y, acc);
+        if (k + 2 < deg) acc = __builtin_fmaf(rdlf(xn, (uint32_t)(k + 3)), w.z, acc);
+        if (k + 3 < deg) acc = __builtin_fmaf(rdlf(xn, (uint32_t)(k + 4)), w.w, acc);
+    };
+    for (int c = 0; c < nck; ++c) {
+        float4 w;
+        if (c < 4) {
+            w = (c == 0) ? wb[0] : (c == 1) ? wb[1] : (c == 2) ? wb[2] : wb[3];
+        } else {
+            w = Wb4[c * B + jb];
+        }
+        chunk(c, w);
+    }
+    S.hbuf[lane] = det_elu(__fadd_rn(lane < B ? w1v : acc, b1v));
+    __builtin_amdgcn_wave_barrier();
+
+    // layers 2..: one straight-line copy per model, picked by scalar branches on the widths (a
+    // schedule with run-time chunk counts needed a scalar branch per chunk, which kept every
+    // 16-B activation read in front of its four FMAs: `buffer_lite` 5 % behind `buffer` at
+    // config 4; a run-time loop over the half batches waited the load counter to zero: 17 %)
+    // (the markers keep the copies apart: with the common start of the `buffer_lite` and
+    // `buffer_lighter` copies hoisted in front of the branch the 4-wave instances spilled 44 VGPRs)
+    float q;
+    if (H == 32) {
+        if (NH == 2) {
+            asm volatile("; buffer_lite");
+            q = lq_stream<PB, kDepth, 8, 2, kEarly>(S, RP, lane, D, deg, w20);
+            asm volatile("; buffer_lite end" : "+v"(q));
+        } else {
+            asm volatile("; buffer_lighter");
+            q = lq_stream<PB, kDepth, 8, 1, kEarly>(S, RP, lane, D, deg, w20);
+            asm volatile("; buffer_lighter end" : "+v"(q));
+        }
+    } else if (H == 16) {
+        asm volatile("; buffer_lighter_2");
+        q = lq_stream<PB, kDepth, 4, 1, kEarly>(S, RP, lane, D, deg, w20);
+        asm volatile("; buffer_lighter_2 end" : "+v"(q));
+    } else {
+        asm volatile("; buffer_lighter_3");
+        q = lq_stream<PB, kDepth, 2, 1, kEarly>(S, RP, lane, D, deg, w20);
+        asm volatile("; buffer_lighter_3 end" : "+v"(q));
+    }
+    __builtin_amdgcn_wave_barrier();
+    // tf.argmin: first minimum (learner.py:145)
+    return lane_argmin_first_seq(q, deg);
+}
+
 // The DQN-buffer decision at node v, memory-resident engine (one wave per SIMD and VGPRs to
 // spare): every weight of layers 2-4 is loaded as the decision starts (MlpPre), one round trip
 // in all.  PRE: the decision follows an arrival that fetched P1 (mlp_preload_node); the pending
@@ -2532,7 +2745,9 @@ __device__ __forceinline__ bool spare_restart(const KParams&, Sim&, RS&, int, ui
 // ---------------------------------------------------------------------------
 // EXPL: the fused policy's action goes through explore_action at both decision sites
 // MB: mlp_action_reg's batch (the memory-resident engine passes 0)
-template <bool MLP, int MB, bool EXPL = false, class RS>
+// LQ: the MLP is one of the reduced DQN-buffer models (lightq_action_reg with P.lq_dims;
+// register-resident instances of their own)
+template <bool MLP, int MB, bool EXPL = false, bool LQ = false, class RS>
 __device__ __forceinline__ uint32_t event_loop(const KParams& P, Sim& S, RS& R, int r, uint32_t max_hops) {
     const int lane = S.lane;
     const LV& L = S.lv;
@@ -2560,6 +2775,8 @@ __device__ __forceinline__ uint32_t event_loop(const KParams& P, Sim& S, RS& R, 
             } else if constexpr (RS::kMem) {
                 MlpPre1 M0;                              // (no arrival came before: nothing prefetched)
                 a = mlp_action_mem<false>(S, pn, (lane < L.W()) ? S.obs[lane] : 0u, M0);
+            } else if constexpr (LQ) {
+                a = lightq_action_reg<MB>(S, pn, (lane < L.W()) ? S.obs[lane] : 0u, P.lq_dims);
             } else {
                 MlpPre1 M0;                              // (never used: see mlp_action_reg)
                 a = mlp_action_reg<MB>(S, pn, (lane < L.W()) ? S.obs[lane] : 0u, M0);
@@ -2633,6 +2850,7 @@ __device__ __forceinline__ uint32_t event_loop(const KParams& P, Sim& S, RS& R, 
                     int a;
                     if (!mlp_mode) a = table_action(S, D.v * NN + D.dst);
                     else if constexpr (RS::kMem) a = mlp_action_mem<true>(S, D.v, D.obs, Mp);
+                    else if constexpr (LQ) a = lightq_action_reg<MB>(S, D.v, D.obs, P.lq_dims);
                     else a = mlp_action_reg<MB>(S, D.v, D.obs, Mp);
                     if (EXPL) a = explore_action(S, H, P.explore_thr, D.d, D.v, a);
                     // (the row handoff: headline +2.1 % in A/B; config 4's MLP instance -2 %, so

@@ -109,12 +109,15 @@ __global__ void __launch_bounds__(64) prisma_reset_kernel_t(KParams P) {
 // step kernels (step_kernel.h): the table-policy instances with the --train / notify_dest
 // code paths are compiled here, the in-kernel DQN-buffer ones in prisma_engine_mlp.hip, the
 // ones without those paths in prisma_engine_lite.hip / prisma_engine_lite_mlp.hip, the exploring
-// ones (prisma_run_explore) in prisma_engine_explore.hip / prisma_engine_explore_mlp.hip
+// ones (prisma_run_explore) in prisma_engine_explore.hip / prisma_engine_explore_mlp.hip, the
+// reduced DQN-buffer models' in prisma_engine_lightq.hip / prisma_engine_explore_lightq.hip
 const void* prisma_pick_step_lite(int fs, int ls, bool tun);
 const void* prisma_pick_step_lite_mlp(int fs, int ls, bool tun);
 const void* prisma_pick_step_ctrl_mlp(int fs, int ls, bool tun);
 const void* prisma_pick_step_explore(int fs, int ls, bool tun);
 const void* prisma_pick_step_explore_mlp(int fs, int ls, bool tun);
+const void* prisma_pick_step_lightq(int fs, int ls, bool tun);
+const void* prisma_pick_step_explore_lightq(int fs, int ls, bool tun);
 static const void* pick_step_ctrl(int fs, int ls, bool tun) { return pick_step<true, false>(fs, ls, tun); }
 
 template <int FS, int LS> const void* reset_kernel() { return (const void*)prisma_reset_kernel_t<FS, LS>; }
@@ -249,6 +252,66 @@ __global__ void prisma_mlp_repack_kernel(const float* __restrict__ w, float* __r
     }
 }
 
+// The reduced DQN-buffer models' weights (PRISMA_POLICY_DQN_LITE ... _DQN_LIGHTER_3; widths B, H and
+// NH hidden layers), row-major [in][out] in the caller's packed buffer (StackedQNet.pack(),
+// models.py:39-227): W1[N][N][B] b1[N][B] Wb[N][D][B] bb[N][B] W2[N][2B][H] b2[N][H]
+// (W3[N][H][H] b3[N][H], NH = 2) Wo[N][H][D] bo[N][D], copied into the interleaved per-node blocks
+// lightq_action_reg reads (engine_core.h, lq_rp_*): rp[v] = [Wb chunks, bb, b1][W2 chunks, b2]
+// ([W3 chunks, b3])[Wo chunks, bo].
+__global__ void prisma_lightq_repack_kernel(const float* __restrict__ w, float* __restrict__ rp, int N, int D, int B,
+                                            int H, int NH) {
+    const int node_f = lq_rp_node_floats(D, B, H, NH);
+    const int l1_f = lq_rp_l1_floats(D, B), kc = (D + 3) / 4;
+    const int f2 = lq_rp_layer_floats(2 * B, H), fh = lq_rp_layer_floats(H, H), fo = lq_rp_layer_floats(H, D);
+    const size_t n = (size_t)N * node_f;
+    const float* b1 = w + (size_t)N * N * B;
+    const float* Wb = b1 + (size_t)N * B;
+    const float* bb = Wb + (size_t)N * D * B;
+    const float* W2 = bb + (size_t)N * B;
+    const float* b2 = W2 + (size_t)N * 2 * B * H;
+    const float* W3 = b2 + (size_t)N * H;                 // (NH = 2 only)
+    const float* b3 = W3 + (size_t)N * H * H;
+    const float* Wo = NH == 2 ? b3 + (size_t)N * H : W3;
+    const float* bo = Wo + (size_t)N * H * D;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int v = (int)(i / node_f);
+        int o = (int)(i - (size_t)v * node_f);
+        float x = 0.0f;                                   // padding (rows k >= D, alignment)
+        if (o < l1_f) {
+            if (o < 4 * B * kc) {
+                const int c = o / (4 * B), r = o - c * 4 * B, j = r >> 2, q = r & 3, k = 4 * c + q;
+                if (k < D) x = Wb[((size_t)v * D + k) * B + j];
+            } else if (o < 4 * B * kc + B) {
+                x = bb[(size_t)v * B + (o - 4 * B * kc)];
+            } else {
+                x = b1[(size_t)v * B + (o - 4 * B * kc - B)];
+            }
+        } else {
+            o -= l1_f;
+            const float *Wl = nullptr, *bl = nullptr;
+            int in = 0, units = 0;
+            if (o < f2) {
+                Wl = W2 + (size_t)v * 2 * B * H; bl = b2 + (size_t)v * H; in = 2 * B; units = H;
+            } else if (NH == 2 && o < f2 + fh) {
+                o -= f2;
+                Wl = W3 + (size_t)v * H * H; bl = b3 + (size_t)v * H; in = H; units = H;
+            } else if (o < f2 + (NH - 1) * fh + fo) {
+                o -= f2 + (NH - 1) * fh;
+                Wl = Wo + (size_t)v * H * D; bl = bo + (size_t)v * D; in = H; units = D;
+            }
+            if (Wl) {
+                if (o < in * units) {
+                    const int c = o / (4 * units), r = o - c * 4 * units, j = r >> 2, q = r & 3;
+                    x = Wl[(size_t)(4 * c + q) * units + j];
+                } else {
+                    x = bl[o - in * units];
+                }
+            }
+        }
+        rp[i] = x;
+    }
+}
+
 // ===========================================================================
 // host side: sizing, validation, C-ABI
 // ===========================================================================
@@ -266,6 +329,9 @@ struct prisma_env {
     const void* k_reset = nullptr;
     const void* k_explore = nullptr;     // exploring instances (prisma_run_explore): register engine
     const void* k_explore_mlp = nullptr; // without the ctrl paths only
+    const void* k_lightq = nullptr;      // reduced DQN-buffer models (PRISMA_POLICY_DQN_LITE ...): register
+    const void* k_explore_lightq = nullptr; // engine without the ctrl paths only
+    float* d_lq_rp = nullptr;            // their interleaved weights (sized for the largest, DQN_LITE)
     float* d_mlp_rp = nullptr;           // interleaved DQN-buffer layers 2-4 (prisma_run, mode 4)
     unsigned char* d_spare = nullptr;    // next-episode images (register engine with auto_reset)
     uint32_t* d_rng = nullptr;           // ns-3 stream table (PRISMA_RNG_NS3, engine_layout.h kMrgPowers)
@@ -1065,6 +1131,8 @@ extern "C" int prisma_create(const prisma_topology_t* topo, const prisma_params_
         if (!ctrl) {
             e->k_explore = prisma_pick_step_explore(L.FS, L.LS, L.tunnels != 0u);
             e->k_explore_mlp = prisma_pick_step_explore_mlp(L.FS, L.LS, L.tunnels != 0u);
+            e->k_lightq = prisma_pick_step_lightq(L.FS, L.LS, L.tunnels != 0u);
+            e->k_explore_lightq = prisma_pick_step_explore_lightq(L.FS, L.LS, L.tunnels != 0u);
         }
         e->kinfo.ctrl = ctrl ? 1u : 0u;
         e->kinfo.relay_ip = (L.tunnels && !ctrl) ? 1u : 0u;
@@ -1081,6 +1149,9 @@ extern "C" int prisma_create(const prisma_topology_t* topo, const prisma_params_
     if (e->k_explore) (void)hipFuncSetAttribute(e->k_explore, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bytes);
     if (e->k_explore_mlp)
         (void)hipFuncSetAttribute(e->k_explore_mlp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_mlp_bytes);
+    if (e->k_lightq) (void)hipFuncSetAttribute(e->k_lightq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_mlp_bytes);
+    if (e->k_explore_lightq)
+        (void)hipFuncSetAttribute(e->k_explore_lightq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_mlp_bytes);
     *out = e;
     return PRISMA_OK;
 }
@@ -1102,7 +1173,8 @@ static KParams base_params(prisma_env_t* e) {
 static int launch(prisma_env_t* e, const void* kern, KParams P, void* stream) {
     (void)hipSetDevice(e->device);
     void* args[] = { &P };
-    const size_t lds = (kern == e->k_step_mlp || kern == e->k_explore_mlp) ? e->lay.lds_mlp_bytes : e->lay.lds_bytes;
+    const bool mlp_kern = kern == e->k_step_mlp || kern == e->k_explore_mlp || kern == e->k_lightq || kern == e->k_explore_lightq;
+    const size_t lds = mlp_kern ? e->lay.lds_mlp_bytes : e->lay.lds_bytes;
     hipError_t err = hipLaunchKernel(kern, dim3((unsigned)e->R), dim3(kWave), args, lds, (hipStream_t)stream);
     if (err == hipSuccess) err = hipGetLastError();
     if (err != hipSuccess) return set_err(PRISMA_ERR_LAUNCH, std::string("kernel launch failed: ") + hipGetErrorString(err));
@@ -1146,14 +1218,46 @@ extern "C" int prisma_step(prisma_env_t* e, const int32_t* actions, int32_t* obs
 static int run_fused(prisma_env_t* e, int32_t policy, const void* policy_data, int32_t max_hops,
                      const uint32_t* explore_thr, void* stream) {
     if (!e->reset_done) return set_err(PRISMA_ERR_STATE, "prisma_reset must be called first");
-    if ((policy != PRISMA_POLICY_TABLE && policy != PRISMA_POLICY_DQN_BUFFER) || !policy_data)
-        return set_err(PRISMA_ERR_ARG, "policy must be PRISMA_POLICY_TABLE (uint8 table) or "
-                                       "PRISMA_POLICY_DQN_BUFFER (fp32 weights), with device data");
+    if (policy < PRISMA_POLICY_TABLE || policy > PRISMA_POLICY_DQN_LIGHTER_3 || !policy_data)
+        return set_err(PRISMA_ERR_ARG, "policy must be PRISMA_POLICY_TABLE (uint8 table), PRISMA_POLICY_DQN_BUFFER or one "
+                                       "of PRISMA_POLICY_DQN_LITE ... _DQN_LIGHTER_3 (fp32 weights), with device data");
     if (max_hops < 1) return set_err(PRISMA_ERR_ARG, "max_hops must be >= 1");
+    const bool lightq = policy >= PRISMA_POLICY_DQN_LITE;
+    if (lightq) {
+        // the reduced models are compiled into instances of their own, which exist for the
+        // register-resident engine without the ctrl paths only (as the exploring ones)
+        if (e->lay.mem)
+            return set_err(PRISMA_ERR_CONFIG, "PRISMA_POLICY_DQN_LITE ... _DQN_LIGHTER_3: the memory-resident engine has no "
+                                              "instances with the reduced DQN-buffer models");
+        if (e->kinfo.ctrl || !e->k_lightq || !e->k_explore_lightq)
+            return set_err(PRISMA_ERR_CONFIG, "PRISMA_POLICY_DQN_LITE ... _DQN_LIGHTER_3: this env runs the step kernels with "
+                                              "the ctrl paths (train, notify_dest, ns-3 streams, or a tunnelled overlay "
+                                              "with log_capacity >= 2^18), which have no instances with the reduced "
+                                              "DQN-buffer models");
+    }
     KParams P = base_params(e);
     if (policy == PRISMA_POLICY_TABLE) {
         P.mode = 2;
         P.table = (const uint8_t*)policy_data;
+    } else if (lightq) {
+        // widths (B, H, NH) of include/prisma.h's table: models.py:184-227, 39-85, 87-133, 135-181
+        static const int kDims[4][3] = { {16, 32, 2}, {16, 32, 1}, {8, 16, 1}, {4, 8, 1} };
+        const int* dm = kDims[policy - PRISMA_POLICY_DQN_LITE];
+        P.mode = 4;
+        P.mlp = (const float*)policy_data;
+        P.lq_dims = lq_pack_dims(dm[0], dm[1], dm[2]);
+        // re-interleaved every call on the caller's stream, as the DQN-buffer weights below
+        const int N = e->lay.N, D = e->lay.max_deg;
+        (void)hipSetDevice(e->device);
+        if (!e->d_lq_rp &&
+            !HIP_OK(hipMalloc(&e->d_lq_rp, (size_t)N * lq_rp_node_floats(D, 16, 32, 2) * sizeof(float))))
+            return set_err(PRISMA_ERR_NOMEM, "hipMalloc of the interleaved reduced-model weights failed");
+        const size_t n = (size_t)N * lq_rp_node_floats(D, dm[0], dm[1], dm[2]);
+        const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 4096);
+        hipLaunchKernelGGL(prisma_lightq_repack_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
+                           P.mlp, e->d_lq_rp, N, D, dm[0], dm[1], dm[2]);
+        if (!HIP_OK(hipGetLastError())) return set_err(PRISMA_ERR_LAUNCH, "repack kernel launch failed");
+        P.mlp_rp = e->d_lq_rp;
     } else {
         P.mode = 4;
         P.mlp = (const float*)policy_data;
@@ -1172,7 +1276,8 @@ static int run_fused(prisma_env_t* e, int32_t policy, const void* policy_data, i
     }
     P.max_hops = max_hops;
     P.explore_thr = explore_thr;
-    const void* kern = explore_thr ? (P.mode == 4 ? e->k_explore_mlp : e->k_explore)
+    const void* kern = lightq ? (explore_thr ? e->k_explore_lightq : e->k_lightq)
+                     : explore_thr ? (P.mode == 4 ? e->k_explore_mlp : e->k_explore)
                                    : (P.mode == 4 ? e->k_step_mlp : e->k_step);
     int rc = launch(e, kern, P, stream);
     // with auto_reset (register engine) the step kernel already continued every replica whose
@@ -1327,6 +1432,7 @@ extern "C" void prisma_destroy(prisma_env_t* e) {
     if (e->d_cnt) (void)hipFree(e->d_cnt);
     if (e->d_lay) (void)hipFree(e->d_lay);
     if (e->d_mlp_rp) (void)hipFree(e->d_mlp_rp);
+    if (e->d_lq_rp) (void)hipFree(e->d_lq_rp);
     if (e->d_spare) (void)hipFree(e->d_spare);
     if (e->d_rng) (void)hipFree(e->d_rng);
     delete e;

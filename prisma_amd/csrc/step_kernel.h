@@ -21,7 +21,9 @@ template <int FS, int LS> struct StepOcc {
 // of the fused policy (engine_core.h explore_action) -- instances of their own, so the greedy
 // ones keep their code and registers.  (The parameter sits in the kernel itself: with the body in
 // a shared inlined function taking the arguments by reference the headline instance came out
-// with 7 more SGPR spill slots and the DQN-buffer one with 16 B more scratch.)
+// with 7 more SGPR spill slots and the DQN-buffer one with 16 B more scratch.)  LQ: the MLP is the
+// reduced DQN-buffer models' decision (engine_core.h lightq_action_reg; widths in KParams::lq_dims)
+// -- instance sets of their own again, greedy and exploring, without the ctrl paths.
 #if PRISMA_WAVE_TIMES
 // diagnostic build only (scripts/wave_times.py): each replica's wave start / end (s_memrealtime,
 // 100 MHz) and hardware ids of its last launch
@@ -41,7 +43,7 @@ __device__ unsigned long long g_wave_times[4 * 65536];
 #define WT_END() do { } while (0)
 #endif
 
-template <int FS, int LS, bool MLP, bool TUN, bool CTRL, bool EXPL = false>
+template <int FS, int LS, bool MLP, bool TUN, bool CTRL, bool EXPL = false, bool LQ = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(StepOcc<FS, LS>::waves)))
 prisma_step_kernel_t(KParams P) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -61,7 +63,7 @@ prisma_step_kernel_t(KParams P) {
     uint32_t budget = (uint32_t)P.max_hops;
     // (4-wave instances only: at 2 waves per SIMD, config 4's, the same thresholds lost 2 %)
     S.prio_total = StepOcc<FS, LS>::waves >= 4 ? budget : 0u;
-    const uint32_t done = event_loop<MLP, StepOcc<FS, LS>::mlp_batch, EXPL>(P, S, R, r, budget);
+    const uint32_t done = event_loop<MLP, StepOcc<FS, LS>::mlp_batch, EXPL, LQ>(P, S, R, r, budget);
     // an episode ended with hop budget left (fused run with auto_reset): the next episode from
     // its prebuilt image, in a second inlined copy of the event loop.  A restart inside the first
     // loop would give its clock and sequence numbers a second incoming value each iteration and
@@ -74,7 +76,7 @@ prisma_step_kernel_t(KParams P) {
         const KParams P2 = *kp;
         if (spare_restart(P2, S, R, r, done, budget)) {
             S.prio_base = done;
-            event_loop<MLP, StepOcc<FS, LS>::mlp_batch, EXPL>(P2, S, R, r, budget);
+            event_loop<MLP, StepOcc<FS, LS>::mlp_batch, EXPL, LQ>(P2, S, R, r, budget);
             // stage out from the reloaded arguments too: with P's pointers kept live across this
             // loop the headline instance spilled 7 VGPRs and reloaded them inside it (round 6:
             // 128 VGPRs + 32 B scratch -> 123 VGPRs, no scratch)
@@ -88,25 +90,27 @@ prisma_step_kernel_t(KParams P) {
 }
 
 // instantiations: flow slots FS in {1,2,4,8} (F <= 512), link slots LS in {1,2,4} (L <= 256)
-template <int FS, int LS, bool CTRL, bool MLP, bool EXPL = false> const void* step_kernel(bool tun) {
+template <int FS, int LS, bool CTRL, bool MLP, bool EXPL = false, bool LQ = false> const void* step_kernel(bool tun) {
     static_assert(!(EXPL && CTRL), "the exploring instances carry no ctrl paths");
-    return tun ? (const void*)prisma_step_kernel_t<FS, LS, MLP, true, CTRL, EXPL>
-               : (const void*)prisma_step_kernel_t<FS, LS, MLP, false, CTRL, EXPL>;
+    static_assert(!LQ || (MLP && !CTRL), "the reduced-model instances are MLP instances without the ctrl paths");
+    return tun ? (const void*)prisma_step_kernel_t<FS, LS, MLP, true, CTRL, EXPL, LQ>
+               : (const void*)prisma_step_kernel_t<FS, LS, MLP, false, CTRL, EXPL, LQ>;
 }
 
 // tun: tunnelled-overlay instance (identity overlays run code without the tunnel paths).
 // One translation unit per (CTRL, MLP) instance set, so the sets compile in parallel:
 // prisma_engine.hip (CTRL, tables), prisma_engine_mlp.hip (CTRL, MLP), prisma_engine_lite.hip
 // and prisma_engine_lite_mlp.hip (without the ctrl paths), prisma_engine_explore.hip and
-// prisma_engine_explore_mlp.hip (EXPL, without the ctrl paths)
-template <bool CTRL, bool MLP, bool EXPL = false>
+// prisma_engine_explore_mlp.hip (EXPL, without the ctrl paths), prisma_engine_lightq.hip and
+// prisma_engine_explore_lightq.hip (LQ, without the ctrl paths)
+template <bool CTRL, bool MLP, bool EXPL = false, bool LQ = false>
 static const void* pick_step(int fs, int ls, bool tun) {
 #ifdef PRISMA_DEV_HEADLINE
     // register-allocation experiments only: compile the headline instance alone
-    return (!CTRL && !MLP && !EXPL && fs == 2 && ls == 1 && !tun) ? (const void*)prisma_step_kernel_t<2, 1, false, false, false>
+    return (!CTRL && !MLP && !EXPL && !LQ && fs == 2 && ls == 1 && !tun) ? (const void*)prisma_step_kernel_t<2, 1, false, false, false>
                                                          : nullptr;
 #else
-#define PK(F_, L_) if (fs == F_ && ls == L_) return step_kernel<F_, L_, CTRL, MLP, EXPL>(tun);
+#define PK(F_, L_) if (fs == F_ && ls == L_) return step_kernel<F_, L_, CTRL, MLP, EXPL, LQ>(tun);
     PK(1, 1) PK(1, 2) PK(1, 4) PK(2, 1) PK(2, 2) PK(2, 4) PK(4, 1) PK(4, 2) PK(4, 4) PK(8, 1) PK(8, 2) PK(8, 4)
 #undef PK
     return nullptr;

@@ -21,12 +21,30 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libprisma_a
 ABI_VERSION = 10
 PRISMA_POLICY_TABLE = 1
 PRISMA_POLICY_DQN_BUFFER = 2
+PRISMA_POLICY_DQN_LITE, PRISMA_POLICY_DQN_LIGHTER, PRISMA_POLICY_DQN_LIGHTER_2, PRISMA_POLICY_DQN_LIGHTER_3 = 3, 4, 5, 6
 PRISMA_ENGINE_AUTO, PRISMA_ENGINE_REGISTER, PRISMA_ENGINE_MEMORY = 0, 1, 2
+
+# run(..., model=): the kind of a packed fp32 policy (StackedQNet kinds) -> (policy id, (B, H, NH)),
+# the widths of include/prisma.h's table (restated here: this module imports no torch)
+MODEL_POLICIES = {
+    "buffer": (PRISMA_POLICY_DQN_BUFFER, (32, 64, 2)),
+    "buffer_lite": (PRISMA_POLICY_DQN_LITE, (16, 32, 2)),
+    "buffer_lighter": (PRISMA_POLICY_DQN_LIGHTER, (16, 32, 1)),
+    "buffer_lighter_2": (PRISMA_POLICY_DQN_LIGHTER_2, (8, 16, 1)),
+    "buffer_lighter_3": (PRISMA_POLICY_DQN_LIGHTER_3, (4, 8, 1)),
+}
 
 
 def dqn_buffer_floats(n: int, d: int) -> int:
     """Length of the packed DQN-buffer weights (include/prisma.h PRISMA_POLICY_DQN_BUFFER)."""
     return n * n * 32 + n * 32 + n * d * 32 + n * 32 + 2 * (n * 64 * 64 + n * 64) + n * 64 * d + n * d
+
+
+def model_floats(model: str, n: int, d: int) -> int:
+    """Length of the packed weights of a DQN-buffer family kind (StackedQNet(kind=model).pack());
+    dqn_buffer_floats for "buffer"."""
+    b, h, nh = MODEL_POLICIES[model][1]
+    return n * (n * b + b + d * b + b + 2 * b * h + h + (nh - 1) * (h * h + h) + h * d + d)
 
 
 class PrismaError(RuntimeError):
@@ -331,11 +349,16 @@ class PrismaEngine:
                                           out.data_ptr(), _stream_handle(stream)))
         return out
 
-    def run(self, policy, max_hops: int, stream=None, explore=None):
+    def run(self, policy, max_hops: int, stream=None, explore=None, model: str = "buffer"):
         """Fused in-kernel policy: every replica executes up to max_hops hops.
 
         policy: a device uint8 [N, N] action table (SP, DQ-routing argmin), or the device fp32
-        packed DQN-buffer weights of StackedQNet(kind="buffer").pack().
+        packed weights of StackedQNet(kind=model).pack().
+
+        model: the kind of a packed fp32 policy, "buffer" (the default) or one of the reduced
+        DQN-buffer models "buffer_lite", "buffer_lighter", "buffer_lighter_2", "buffer_lighter_3"
+        (MODEL_POLICIES; the register-resident engine without the ctrl paths only).  The policy must
+        have model_floats(model, n_nodes, max_deg) elements.  Ignored for a table.
 
         explore: None (greedy), or the epsilons of an epsilon-greedy rollout (prisma_run_explore;
         prisma_amd/explore.py restates its draw rule): a scalar, or a float tensor / array
@@ -345,10 +368,15 @@ class PrismaEngine:
         n, d = self.topo.n_nodes, self.topo.max_deg
         if not policy.is_cuda:
             raise PrismaError("policy data must live on the device")
+        if model not in MODEL_POLICIES:
+            raise PrismaError(f"model must be one of {', '.join(MODEL_POLICIES)}")
         if policy.dtype == torch.uint8 and tuple(policy.shape) == (n, n):
             kind = PRISMA_POLICY_TABLE
-        elif policy.dtype == torch.float32 and policy.dim() == 1 and policy.numel() == dqn_buffer_floats(n, d):
-            kind = PRISMA_POLICY_DQN_BUFFER
+        elif policy.dtype == torch.float32 and policy.dim() == 1 and policy.numel() == model_floats(model, n, d):
+            kind = MODEL_POLICIES[model][0]
+        elif model != "buffer":
+            raise PrismaError(f"policy must be a uint8 [n_nodes, n_nodes] table or the packed fp32 weights of model "
+                              f"{model!r}: {model_floats(model, n, d)} elements")
         else:
             raise PrismaError("policy must be a uint8 [n_nodes, n_nodes] table or packed fp32 DQN-buffer weights")
         self._policy_keep = policy.contiguous()

@@ -11,6 +11,9 @@
   one-hot branch Dense(32) || LayerNormalization(axis=1, no centre/scale,
   epsilon 1e-3 = Keras default) of the deg buffer values -> Dense(32); concat
   -> Dense(64) -> Dense(64) -> Dense(deg), ELU everywhere.
+* ``StackedQNet(kind="buffer_lite" | "buffer_lighter" | "buffer_lighter_2" |
+  "buffer_lighter_3")`` — models.py:184-227, 39-85, 87-133, 135-181: DQN_buffer_model's
+  structure at the widths of ``BUFFER_DIMS`` (branch width B, hidden width H, NH hidden layers).
 * action = argmin_a Q(obs)[a] (learner.py:142-145), first index on ties,
   greedy (train=0, forwarder.py:183-186).
 
@@ -29,6 +32,7 @@ from typing import Optional
 import numpy as np
 import torch
 
+from .engine import MODEL_POLICIES, model_floats
 from .topology import Topology, sp_next_hop_table
 
 
@@ -46,6 +50,20 @@ class SPPolicy:
         return self.table[node.long(), dst].to(torch.int32)
 
 
+# DQN-buffer family: kind -> (B, H, NH): both first-layer branches are Dense(B), the concat goes
+# through NH Dense(H) layers, then Dense(deg) (engine.MODEL_POLICIES holds the table, beside the
+# policy ids)
+BUFFER_DIMS = {k: dims for k, (_, dims) in MODEL_POLICIES.items()}
+# Length of pack() for a family kind on n nodes with largest overlay degree d (include/prisma.h
+# PRISMA_POLICY_DQN_BUFFER, _DQN_LITE ... _DQN_LIGHTER_3)
+buffer_floats = model_floats
+
+
+def buffer_layer_names(kind: str) -> list:
+    """Parameter names of a family kind's Dense layers in Keras's layer order (W4 = the output)."""
+    return ["W1", "Wb", "W2"] + (["W3"] if BUFFER_DIMS[kind][2] == 2 else []) + ["W4"]
+
+
 def _he_uniform(gen: torch.Generator, fan_in: int, shape) -> torch.Tensor:
     lim = math.sqrt(6.0 / fan_in)
     return (torch.rand(shape, generator=gen, dtype=torch.float64) * 2.0 - 1.0).mul_(lim).to(torch.float32)
@@ -56,9 +74,13 @@ class StackedQNet(torch.nn.Module):
 
     def __init__(self, topo: Topology, kind: str = "routing", seed: int = 0, device="cuda"):
         super().__init__()
-        if kind not in ("routing", "buffer"):
-            raise ValueError("kind must be 'routing' or 'buffer'")
+        if kind != "routing" and kind not in BUFFER_DIMS:
+            raise ValueError("kind must be 'routing' or one of " + ", ".join(repr(k) for k in BUFFER_DIMS))
         self.kind = kind
+        self.is_buffer = kind != "routing"
+        # widths (the routing model's are the 64-wide ones without the buffers branch)
+        Bw, Hw, NH = BUFFER_DIMS.get(kind, (32, 64, 2))
+        self.dims = (Bw, Hw, NH)
         self.N = topo.n_nodes
         self.topo_overlay_nodes = topo.overlay_nodes.astype(np.int64)
         self.D = topo.max_deg
@@ -81,14 +103,15 @@ class StackedQNet(torch.nn.Module):
             return torch.nn.Parameter(W), torch.nn.Parameter(b)
 
         ones = [topo.n_overlay] * N                                 # one_hot(dst, numNodes)
-        self.W1, self.b1 = dense(ones, N, 32)                       # one-hot(dst) branch
-        if kind == "buffer":
-            self.Wb, self.bb = dense(topo.degrees, D, 32)           # buffers branch (deg inputs)
-            self.W2, self.b2 = dense([64] * N, 64, 64)
+        self.W1, self.b1 = dense(ones, N, Bw)                       # one-hot(dst) branch
+        if self.is_buffer:
+            self.Wb, self.bb = dense(topo.degrees, D, Bw)           # buffers branch (deg inputs)
+            self.W2, self.b2 = dense([2 * Bw] * N, 2 * Bw, Hw)
         else:
-            self.W2, self.b2 = dense([32] * N, 32, 64)
-        self.W3, self.b3 = dense([64] * N, 64, 64)
-        self.W4, self.b4 = dense([64] * N, 64, [int(d) for d in topo.degrees], D)
+            self.W2, self.b2 = dense([Bw] * N, Bw, Hw)
+        if NH == 2:
+            self.W3, self.b3 = dense([Hw] * N, Hw, Hw)
+        self.W4, self.b4 = dense([Hw] * N, Hw, [int(d) for d in topo.degrees], D)
         self.to(device)
 
     @staticmethod
@@ -101,7 +124,7 @@ class StackedQNet(torch.nn.Module):
         dst = obs[:, 0].long()
         elu = torch.nn.functional.elu
         h1 = elu(self.W1[node, dst] + self.b1[node])                # one_hot @ W1 == row gather
-        if self.kind == "buffer":
+        if self.is_buffer:
             D = self.D
             deg = self.deg[node]
             x = obs[:, 1:1 + D].to(torch.float32)
@@ -116,7 +139,8 @@ class StackedQNet(torch.nn.Module):
         else:
             h = h1
         h = elu(self._lin(h, self.W2, self.b2, node))
-        h = elu(self._lin(h, self.W3, self.b3, node))
+        if self.dims[2] == 2:
+            h = elu(self._lin(h, self.W3, self.b3, node))
         q = elu(self._lin(h, self.W4, self.b4, node))
         pad = torch.arange(self.D, device=q.device)[None, :] >= self.deg[node][:, None]
         return q.masked_fill(pad, float("inf"))
@@ -127,12 +151,14 @@ class StackedQNet(torch.nn.Module):
 
     @torch.no_grad()
     def pack(self) -> torch.Tensor:
-        """Flat fp32 weights for the in-kernel DQN-buffer policy (PRISMA_POLICY_DQN_BUFFER):
-        W1[N][N][32] b1[N][32] Wb[N][D][32] bb[N][32] W2[N][64][64] b2[N][64] W3[N][64][64]
-        b3[N][64] W4[N][64][D] b4[N][D] (include/prisma.h)."""
-        if self.kind != "buffer":
-            raise ValueError("pack() is the DQN-buffer layout (kind='buffer')")
-        parts = [self.W1, self.b1, self.Wb, self.bb, self.W2, self.b2, self.W3, self.b3, self.W4, self.b4]
+        """Flat fp32 weights for the in-kernel DQN-buffer family policies (PRISMA_POLICY_DQN_BUFFER,
+        _DQN_LITE, _DQN_LIGHTER, _DQN_LIGHTER_2, _DQN_LIGHTER_3), row-major with (B, H, NH) =
+        BUFFER_DIMS[kind]: W1[N][N][B] b1[N][B] Wb[N][D][B] bb[N][B] W2[N][2B][H] b2[N][H],
+        W3[N][H][H] b3[N][H] only when NH = 2, W4[N][H][D] b4[N][D] (include/prisma.h names the
+        last pair Wo, bo); buffer_floats(kind, N, D) elements."""
+        if not self.is_buffer:
+            raise ValueError("pack() is the DQN-buffer family's layout (kind='buffer', 'buffer_lite', ...)")
+        parts = [p for wn in buffer_layer_names(self.kind) for p in (getattr(self, wn), getattr(self, "b" + wn[1:]))]
         return torch.cat([p.detach().to(torch.float32).contiguous().flatten() for p in parts])
 
     @torch.no_grad()

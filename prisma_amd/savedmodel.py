@@ -312,6 +312,15 @@ def node_index(folder: str) -> int:
     return int(folder.split("_")[-1][4:])
 
 
+def _layer_names(kind: str) -> List[str]:
+    """StackedQNet parameter names of `kind`'s Dense layers in Keras's layer order: 4 for the
+    routing model, 3 + NH for the DQN-buffer family (the two first-layer branches, NH hidden
+    layers, the output; policies.BUFFER_DIMS: the reduced models with one hidden layer,
+    models.py:39-181, have no W3)."""
+    from .policies import buffer_layer_names
+    return ["W1", "W2", "W3", "W4"] if kind == "routing" else buffer_layer_names(kind)
+
+
 def load_q_networks(path: str, topo, kind: str = "buffer", device="cpu", node: int = -1):
     """utils.load_model(path, node_index) for every saved ``node<i>`` folder under `path`, into a
     StackedQNet(topo, kind) (node i = underlay node id, as save_all_models numbers them).  Nodes
@@ -322,7 +331,7 @@ def load_q_networks(path: str, topo, kind: str = "buffer", device="cpu", node: i
     with torch.no_grad():
         for p in net.parameters():
             p.zero_()
-        names = (["W1", "Wb", "W2", "W3", "W4"] if kind == "buffer" else ["W1", "W2", "W3", "W4"])
+        names = _layer_names(kind)
         loaded = []
         for item in sorted(os.listdir(path)):
             i = node_index(item)
@@ -346,7 +355,7 @@ def load_q_networks(path: str, topo, kind: str = "buffer", device="cpu", node: i
 def save_q_networks(net, path: str, nodes: Iterable[int]) -> None:
     """The inverse: node<i>/variables/variables.* bundles of StackedQNet `net` in Keras's keys
     (utils.save_all_models' folder layout; variables only, no graph)."""
-    names = (["W1", "Wb", "W2", "W3", "W4"] if net.kind == "buffer" else ["W1", "W2", "W3", "W4"])
+    names = _layer_names(net.kind)
     deg = net.deg.cpu().numpy()
     for i in nodes:
         t = {}

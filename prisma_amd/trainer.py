@@ -99,7 +99,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .policies import StackedQNet
+from .policies import BUFFER_DIMS, StackedQNet
 from .records import EBIT_NAMES
 from .topology import Topology
 
@@ -248,11 +248,16 @@ def convert_bps_to_data_rate(text: str) -> float:
 
 
 def nn_param_count(topo: Topology, u: int, kind: str) -> int:
-    """Trainable parameters of node u's Keras model (models.py:258-306, 360-392); the
-    LayerNormalization has none (center=False, scale=False)."""
+    """Trainable parameters of node u's Keras model (models.py:258-306, 360-392, and the reduced
+    DQN-buffer models :39-227 at policies.BUFFER_DIMS' widths); the LayerNormalization has none
+    (center=False, scale=False)."""
     no, d = topo.n_overlay, int(topo.degrees[u])
-    n = no * 32 + 32 + 64 * 64 + 64 + 64 * d + d
-    return n + ((d * 32 + 32) + (64 * 64 + 64) if kind == "buffer" else (32 * 64 + 64))
+    if kind == "routing":
+        return no * 32 + 32 + 32 * 64 + 64 + 64 * 64 + 64 + 64 * d + d
+    if kind not in BUFFER_DIMS:
+        raise ValueError(f"unknown model kind {kind!r}")
+    b, h, nh = BUFFER_DIMS[kind]
+    return (no * b + b) + (d * b + b) + (2 * b * h + h) + (nh - 1) * (h * h + h) + (h * d + d)
 
 
 class QRoutingTrainer:
@@ -826,10 +831,11 @@ def train_fused(env, trainer: QRoutingTrainer, launches: int, hops_per_launch: i
     ``hops_per_launch`` hops per replica (VecRoutingEnv.run(..., explore=...), the exploring step
     kernels) instead of one decision per replica per launch as in train().  Per launch: the fused
     policy is refreshed from the online networks (argmin_table() for kind="routing", pack() for
-    "buffer"), the env runs with the nodes' current epsilons (explore_eps(): constant over the
-    launch, where the reference re-reads its schedule per decision), the replicas' clocks move to
-    the counters', the launch's completed transitions enter the buffers, the due syncs run, and
-    every ``train_every`` launches a training step.  Returns the mean losses of the training steps.
+    "buffer" and the reduced DQN-buffer kinds, run with model=kind), the env runs with the nodes'
+    current epsilons (explore_eps(): constant over the launch, where the reference re-reads its
+    schedule per decision), the replicas' clocks move to the counters', the launch's completed
+    transitions enter the buffers, the due syncs run, and every ``train_every`` launches a training
+    step.  Returns the mean losses of the training steps.
 
     "ideal" signalling only (a transition enters the buffer when it completes; the others wait for
     signalling packets the fused rollout does not hand out).  A launch that writes more records
@@ -847,8 +853,10 @@ def train_fused(env, trainer: QRoutingTrainer, launches: int, hops_per_launch: i
     cap = env.engine.log_capacity
     losses = []
     for k in range(launches):
-        policy = trainer.q.argmin_table() if trainer.kind == "routing" else trainer.q.pack()
-        env.run(policy, hops_per_launch, explore=trainer.explore_eps())
+        if trainer.kind == "routing":
+            env.run(trainer.q.argmin_table(), hops_per_launch, explore=trainer.explore_eps())
+        else:
+            env.run(trainer.q.pack(), hops_per_launch, explore=trainer.explore_eps(), model=trainer.kind)
         cf = env._counter_fields()
         # one host read: replicas over the log's size, and replicas per PRISMA_EBIT_* bit
         over, *per_bit = torch.stack([((cf["dec_count"] - env._consumed) >= cap).sum()]
