@@ -399,6 +399,53 @@ int prisma_run(prisma_env_t* env, int32_t policy, const void* policy_data,
 int prisma_run_explore(prisma_env_t* env, int32_t policy, const void* policy_data,
                        int32_t max_hops, const uint32_t* explore_thr, void* stream);
 
+/* The layout of an action history (prisma_run_explore_smart): one uint32
+ * count per (node, action), T = the sum of the overlay degrees per replica.
+ * row_out (host int32 [n_nodes + 1], or NULL): row[v] is the offset of node
+ * v's first action, by underlay id, row[v + 1] - row[v] its overlay degree
+ * (empty for a node outside the overlay), row[n_nodes] = T.  total_out: T.
+ * Works for every env, whichever engine it runs on. */
+int prisma_action_history_layout(prisma_env_t* env, int32_t* row_out, int32_t* total_out);
+
+/* prisma_run_explore with history-weighted ("smart") exploration: the same
+ * contract in every respect (policies, the repack, auto_reset, the
+ * next-episode restart, explore_thr, the draw and the hit test), but an
+ * exploring decision picks action i with probability proportional to
+ * 1 - hist[i] / sum(hist) over the deciding node's row of a caller-owned
+ * count of the actions taken, instead of uniformly, and every data decision
+ * counts its action.  action_hist: device uint32 [n_replicas][T], laid out by
+ * prisma_action_history_layout; the library never initialises it (the
+ * reference starts at ones) and keeps no copy: it lives as long as the
+ * caller's buffer, over launches and episodes.  For the decision of
+ * prisma_run_explore's rule (d, e, v, deg, g, r, c as there):
+ *
+ *   hit  = (c[0] >> 8) < explore_thr[v]
+ *   h_i  = action_hist[r][row[v] + i], i in [0, deg);  nb = sum h_i (uint64)
+ *   w_i  = nb - h_i;  W = (deg - 1) * nb
+ *   pick = W == 0 ? (uint32)(((uint64)c[1] * deg) >> 32)
+ *                 : min { i : w_0 + ... + w_i > u },
+ *          u = (uint64)(((unsigned __int128)(((uint64)c[1] << 32) | c[2]) * W) >> 64)
+ *   a    = hit ? pick : g
+ *   then, if 0 <= a < deg:  action_hist[r][row[v] + a] += 1
+ *
+ * w_i / W = (1 - h_i / nb) / (deg - 1).  W == 0 (deg = 1, or a row of zeros)
+ * is prisma_run_explore's uniform pick.  The count is taken at every data
+ * decision, explored or greedy, also where explore_thr[v] = 0 skips the
+ * draw; a policy action outside [0, deg) (the packet is discarded) counts
+ * nothing, and neither do destination arrivals and control packets.  The
+ * counts are uint32 and wrap: with deg <= 55, W < 2^38, and the caller must
+ * re-base a row (e.g. halve it) before one of its counts reaches 2^32.  Only
+ * replica r's wave touches action_hist[r] during a launch; a host or another
+ * stream must not write the buffer while a launch that uses it is in flight.
+ * NULL explore_thr or action_hist, or hist_words != n_replicas * T:
+ * PRISMA_ERR_ARG.  The kernels exist where prisma_run_explore's do: an env
+ * whose prisma_kernel_info reports ctrl = 1 or the memory-resident engine
+ * gets PRISMA_ERR_CONFIG.  (Added without an ABI version change: no struct or
+ * signature moved.) */
+int prisma_run_explore_smart(prisma_env_t* env, int32_t policy, const void* policy_data,
+                             int32_t max_hops, const uint32_t* explore_thr,
+                             uint32_t* action_hist, uint64_t hist_words, void* stream);
+
 /* Copy per-replica counters (n_replicas entries) to host memory.
  * Synchronises `stream`. */
 int prisma_read_counters(prisma_env_t* env, prisma_counters_t* host_out,

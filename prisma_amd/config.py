@@ -18,7 +18,7 @@ DEFAULTS = dict(
     movingAverageObsSize=5, activateUnderlayTraffic=0, pingAsObs=1, pingPacketIntervalTime=0.2,
     load_factor=1.0, topology_name="abilene", traffic_matrix_index=0, max_out_buffer_size=16260,
     link_delay=1, packet_size=512, link_cap=500000, agent_type="dqn_buffer", signaling_type="ideal",
-    loss_penalty_type="fixed", signalingSim=0, sync_step=1.0, bigSignalingSize=512,
+    loss_penalty_type="fixed", signalingSim=0, sync_step=1.0, bigSignalingSize=512, smart_exploration=0,
 )
 SIGNALING_TYPES = {"ideal": 0, "NN": 1, "target": 2}      # include/prisma.h PRISMA_SIGNALING_*
 RNG_MODES = {"philox": 0, "ns3": 1}                           # include/prisma.h PRISMA_RNG_*
@@ -62,6 +62,9 @@ def build_parser() -> argparse.ArgumentParser:
     g3.add_argument("--loss_penalty_type", type=str, choices=["None", "fixed"], default=DEFAULTS["loss_penalty_type"])
     g3.add_argument("--bigSignalingSize", type=int, default=DEFAULTS["bigSignalingSize"])
     g3.add_argument("--sync_step", type=float, default=DEFAULTS["sync_step"])
+    # argument_parser.py:76: explore with probability proportional to 1 - (an action's share of the
+    # actions taken); QRoutingTrainer(smart_exploration=...)
+    g3.add_argument("--smart_exploration", type=int, default=DEFAULTS["smart_exploration"])
     return p
 
 

@@ -107,6 +107,8 @@ struct KParams {
                                  // null; last, so the other instances' kernarg offsets stay put
     uint32_t lq_dims;            // reduced DQN-buffer models (the LQ instances): lq_pack_dims(B, H, NH) of the
                                  // weights in `mlp` / `mlp_rp`, else 0; after explore_thr for the same reason
+    uint32_t* action_hist;       // [R][T] per-action counts (prisma_run_explore_smart, the smart instances), or
+                                 // null; T = ovrow[N].  Last again: no other instance's kernarg offset moves
 };
 
 // ---------------------------------------------------------------------------
@@ -2666,6 +2668,79 @@ __device__ __forceinline__ int explore_action(const Sim& S, const Hot& H, const 
     return (int)(uint32_t)(((uint64_t)c1 * deg) >> 32);
 }
 
+// History-weighted ("smart") exploration (prisma_run_explore_smart, the smart instances;
+// include/prisma.h states the rule): the same draw and hit test as explore_action, but a hit
+// picks action i with probability w_i / W, w_i = nb - h_i, nb = sum h, W = (deg - 1) nb, over the
+// node's row of the caller's per-replica action counts, and every data decision with a valid
+// action -- explored or greedy, thr = 0 included -- adds one to its count.
+//
+// The hit branch is scalar (d, v, thr[v] and the draw are wave-uniform), so all 64 lanes are
+// active in it.  Lane i < deg loads h_i (one coalesced load; lanes >= deg load nothing and
+// contribute 0); one inclusive 64-bit DPP scan of h gives P_i = h_0 + ... + h_i, whose last lane is
+// nb (the reduction), and the prefix of the weights follows without a second scan:
+// w_0 + ... + w_i = (i + 1) nb - P_i for i < deg, and W from lane deg - 1 on.  A ballot of
+// prefix > u plus find-first is the pick: u < W, so a lane below deg always matches first.
+//
+// The count is bumped by lane a, with the address lane a also loads from, and both accesses are
+// relaxed agent-scope atomics: the add is executed in L2 and the loads bypass the CU's L1, so a
+// pick sees the wave's own earlier increments (same thread, same address: coherence order).
+// Only replica r's wave touches hist[r].
+template <class T> __device__ __forceinline__ T* rfl_ptr(T* p) {     // a wave-uniform pointer, into SGPRs
+    return (T*)mk64(rfl(lo32((int64_t)p)), rfl(hi32((int64_t)p)));
+}
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ uint64_t dpp_scan_step_u64(uint64_t v) {
+    // lanes with no source (row start, masked rows) take 0
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, ROW_MASK, 0xf, false);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), CTRL, ROW_MASK, 0xf, false);
+    return v + (uint64_t)mk64(lo, hi);
+}
+// inclusive prefix sum over the 64 lanes (all active)
+__device__ __forceinline__ uint64_t wave_scan_u64(uint64_t v) {
+    v = dpp_scan_step_u64<0x111, 0xF>(v);   // row_shr:1
+    v = dpp_scan_step_u64<0x112, 0xF>(v);   // row_shr:2
+    v = dpp_scan_step_u64<0x114, 0xF>(v);   // row_shr:4
+    v = dpp_scan_step_u64<0x118, 0xF>(v);   // row_shr:8
+    v = dpp_scan_step_u64<0x142, 0xA>(v);   // row_bcast:15 into rows 1 and 3
+    v = dpp_scan_step_u64<0x143, 0xC>(v);   // row_bcast:31 into rows 2 and 3
+    return v;
+}
+
+__device__ __forceinline__ int smart_explore_action(const Sim& S, const Hot& H, const uint32_t* __restrict__ thr,
+                                                    uint32_t* hist, int r, uint32_t d, uint32_t v, int g) {
+    v = rfl(v);
+    const uint32_t t = rfl(thr[v]);
+    const uint32_t r0 = rfl((uint32_t)t_ovrow(S, v));
+    const uint32_t deg = rfl((uint32_t)t_ovrow(S, v + 1)) - r0;
+    const uint32_t lane = (uint32_t)S.lane;
+    // the node's row of this replica's counts
+    uint32_t* row = hist + (size_t)(uint32_t)r * rfl((uint32_t)t_ovrow(S, (uint32_t)S.lv.N())) + r0;
+    uint32_t a = (uint32_t)g;
+    if (t != 0u) {
+        uint32_t c[4] = { rfl(d), 0u, H.episode, 2u };
+        uint32_t k0 = S.lv.seed_lo(), k1 = S.gid;
+        asm volatile("" : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]), "+v"(k0), "+v"(k1));
+        philox4x32_10(c, k0, k1);
+        const uint32_t c0 = rfl(c[0]), c1 = rfl(c[1]), c2 = rfl(c[2]);
+        if ((c0 >> 8) < t) {
+            uint32_t h = 0u;
+            if (lane < deg) h = __hip_atomic_load(row + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const uint64_t ps = wave_scan_u64((uint64_t)h);
+            const uint64_t nb = (uint64_t)mk64(rdl((uint32_t)ps, 63u), rdl((uint32_t)(ps >> 32), 63u));
+            const uint64_t W = (uint64_t)(deg - 1u) * nb;
+            if (W == 0u) {
+                a = (uint32_t)(((uint64_t)c1 * deg) >> 32);
+            } else {
+                const uint64_t u = __umul64hi(((uint64_t)c1 << 32) | c2, W);
+                const uint32_t n = lane < deg ? lane + 1u : deg;
+                a = (uint32_t)__builtin_ctzll(__ballot((uint64_t)n * nb - ps > u));
+            }
+        }
+    }
+    if (lane == a && a < deg) (void)__hip_atomic_fetch_add(row + lane, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return (int)a;
+}
+
 template <int FS, int LS>
 __device__ __forceinline__ void stage_in(unsigned char* lds, const KParams& P, int r, int lane, Regs<FS, LS>& R) {
     CLayout& LC = *(CLayout*)P.lay;
@@ -2743,11 +2818,12 @@ __device__ __forceinline__ bool spare_restart(const KParams&, Sim&, RS&, int, ui
 // then one discrete event per iteration until max_hops hops, a decision that
 // needs an external action, or the end of the episode; publish the outputs.
 // ---------------------------------------------------------------------------
-// EXPL: the fused policy's action goes through explore_action at both decision sites
+// EXPL: the fused policy's action goes through explore_action (1) or smart_explore_action (2)
+// at both decision sites
 // MB: mlp_action_reg's batch (the memory-resident engine passes 0)
 // LQ: the MLP is one of the reduced DQN-buffer models (lightq_action_reg with P.lq_dims;
 // register-resident instances of their own)
-template <bool MLP, int MB, bool EXPL = false, bool LQ = false, class RS>
+template <bool MLP, int MB, int EXPL = 0, bool LQ = false, class RS>
 __device__ __forceinline__ uint32_t event_loop(const KParams& P, Sim& S, RS& R, int r, uint32_t max_hops) {
     const int lane = S.lane;
     const LV& L = S.lv;
@@ -2782,7 +2858,8 @@ __device__ __forceinline__ uint32_t event_loop(const KParams& P, Sim& S, RS& R, 
                 a = mlp_action_reg<MB>(S, pn, (lane < L.W()) ? S.obs[lane] : 0u, M0);
             }
             // (the instances without the ctrl paths: every pending notification is a data decision)
-            if (EXPL) a = explore_action(S, H, P.explore_thr, u_ld32(&S.h->pend_dec), pn, a);
+            if (EXPL == 1) a = explore_action(S, H, P.explore_thr, u_ld32(&S.h->pend_dec), pn, a);
+            if (EXPL == 2) a = smart_explore_action(S, H, P.explore_thr, P.action_hist, r, u_ld32(&S.h->pend_dec), pn, a);
             H.hops_launch += finish_pending(S, R, H, a);
         } else if (P.actions) {
             // (counted like a fused hop: hops_total is the hops since reset on every path)
@@ -2852,7 +2929,8 @@ __device__ __forceinline__ uint32_t event_loop(const KParams& P, Sim& S, RS& R, 
                     else if constexpr (RS::kMem) a = mlp_action_mem<true>(S, D.v, D.obs, Mp);
                     else if constexpr (LQ) a = lightq_action_reg<MB>(S, D.v, D.obs, P.lq_dims);
                     else a = mlp_action_reg<MB>(S, D.v, D.obs, Mp);
-                    if (EXPL) a = explore_action(S, H, P.explore_thr, D.d, D.v, a);
+                    if (EXPL == 1) a = explore_action(S, H, P.explore_thr, D.d, D.v, a);
+                    if (EXPL == 2) a = smart_explore_action(S, H, P.explore_thr, P.action_hist, r, D.d, D.v, a);
                     // (the row handoff: headline +2.1 % in A/B; config 4's MLP instance -2 %, so
                     // the MLP instances read the row again)
                     apply_decision<!RS::kMem && !MLP>(S, R, H, D.x, D.dst, D.start, D.uid, D.v, D.d, a, true,

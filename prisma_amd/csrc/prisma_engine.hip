@@ -110,7 +110,9 @@ __global__ void __launch_bounds__(64) prisma_reset_kernel_t(KParams P) {
 // code paths are compiled here, the in-kernel DQN-buffer ones in prisma_engine_mlp.hip, the
 // ones without those paths in prisma_engine_lite.hip / prisma_engine_lite_mlp.hip, the exploring
 // ones (prisma_run_explore) in prisma_engine_explore.hip / prisma_engine_explore_mlp.hip, the
-// reduced DQN-buffer models' in prisma_engine_lightq.hip / prisma_engine_explore_lightq.hip
+// reduced DQN-buffer models' in prisma_engine_lightq.hip / prisma_engine_explore_lightq.hip, the
+// ones with history-weighted exploration (prisma_run_explore_smart) in prisma_engine_smart.hip /
+// prisma_engine_smart_mlp.hip / prisma_engine_smart_lightq.hip
 const void* prisma_pick_step_lite(int fs, int ls, bool tun);
 const void* prisma_pick_step_lite_mlp(int fs, int ls, bool tun);
 const void* prisma_pick_step_ctrl_mlp(int fs, int ls, bool tun);
@@ -118,6 +120,9 @@ const void* prisma_pick_step_explore(int fs, int ls, bool tun);
 const void* prisma_pick_step_explore_mlp(int fs, int ls, bool tun);
 const void* prisma_pick_step_lightq(int fs, int ls, bool tun);
 const void* prisma_pick_step_explore_lightq(int fs, int ls, bool tun);
+const void* prisma_pick_step_smart(int fs, int ls, bool tun);
+const void* prisma_pick_step_smart_mlp(int fs, int ls, bool tun);
+const void* prisma_pick_step_smart_lightq(int fs, int ls, bool tun);
 static const void* pick_step_ctrl(int fs, int ls, bool tun) { return pick_step<true, false>(fs, ls, tun); }
 
 template <int FS, int LS> const void* reset_kernel() { return (const void*)prisma_reset_kernel_t<FS, LS>; }
@@ -331,6 +336,10 @@ struct prisma_env {
     const void* k_explore_mlp = nullptr; // without the ctrl paths only
     const void* k_lightq = nullptr;      // reduced DQN-buffer models (PRISMA_POLICY_DQN_LITE ...): register
     const void* k_explore_lightq = nullptr; // engine without the ctrl paths only
+    const void* k_smart = nullptr;       // history-weighted exploration (prisma_run_explore_smart): register
+    const void* k_smart_mlp = nullptr;   // engine without the ctrl paths only
+    const void* k_smart_lightq = nullptr;
+    std::vector<int32_t> ovrow;          // [N + 1] overlay CSR rows by underlay id (prisma_action_history_layout)
     float* d_lq_rp = nullptr;            // their interleaved weights (sized for the largest, DQN_LITE)
     float* d_mlp_rp = nullptr;           // interleaved DQN-buffer layers 2-4 (prisma_run, mode 4)
     unsigned char* d_spare = nullptr;    // next-episode images (register engine with auto_reset)
@@ -1051,6 +1060,11 @@ extern "C" int prisma_create(const prisma_topology_t* topo, const prisma_params_
     e->device = device;
     e->R = n_replicas;
     e->lay = L;
+    {
+        OverlayPlan OP;                      // (build_layout has validated the overlay)
+        if ((rc = plan_overlay(topo, OP)) != 0) { delete e; return rc; }
+        e->ovrow = OP.ovrow;
+    }
     size_t sb = (size_t)L.state_bytes * n_replicas;
     size_t lb = (size_t)L.log_cap * L.rec_bytes * n_replicas;
     if (!HIP_OK(hipMalloc(&e->d_state, sb)) || !HIP_OK(hipMalloc(&e->d_topo, L.topo_bytes)) ||
@@ -1133,6 +1147,9 @@ extern "C" int prisma_create(const prisma_topology_t* topo, const prisma_params_
             e->k_explore_mlp = prisma_pick_step_explore_mlp(L.FS, L.LS, L.tunnels != 0u);
             e->k_lightq = prisma_pick_step_lightq(L.FS, L.LS, L.tunnels != 0u);
             e->k_explore_lightq = prisma_pick_step_explore_lightq(L.FS, L.LS, L.tunnels != 0u);
+            e->k_smart = prisma_pick_step_smart(L.FS, L.LS, L.tunnels != 0u);
+            e->k_smart_mlp = prisma_pick_step_smart_mlp(L.FS, L.LS, L.tunnels != 0u);
+            e->k_smart_lightq = prisma_pick_step_smart_lightq(L.FS, L.LS, L.tunnels != 0u);
         }
         e->kinfo.ctrl = ctrl ? 1u : 0u;
         e->kinfo.relay_ip = (L.tunnels && !ctrl) ? 1u : 0u;
@@ -1152,6 +1169,11 @@ extern "C" int prisma_create(const prisma_topology_t* topo, const prisma_params_
     if (e->k_lightq) (void)hipFuncSetAttribute(e->k_lightq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_mlp_bytes);
     if (e->k_explore_lightq)
         (void)hipFuncSetAttribute(e->k_explore_lightq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_mlp_bytes);
+    if (e->k_smart) (void)hipFuncSetAttribute(e->k_smart, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bytes);
+    if (e->k_smart_mlp)
+        (void)hipFuncSetAttribute(e->k_smart_mlp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_mlp_bytes);
+    if (e->k_smart_lightq)
+        (void)hipFuncSetAttribute(e->k_smart_lightq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_mlp_bytes);
     *out = e;
     return PRISMA_OK;
 }
@@ -1173,7 +1195,8 @@ static KParams base_params(prisma_env_t* e) {
 static int launch(prisma_env_t* e, const void* kern, KParams P, void* stream) {
     (void)hipSetDevice(e->device);
     void* args[] = { &P };
-    const bool mlp_kern = kern == e->k_step_mlp || kern == e->k_explore_mlp || kern == e->k_lightq || kern == e->k_explore_lightq;
+    const bool mlp_kern = kern == e->k_step_mlp || kern == e->k_explore_mlp || kern == e->k_lightq ||
+                          kern == e->k_explore_lightq || kern == e->k_smart_mlp || kern == e->k_smart_lightq;
     const size_t lds = mlp_kern ? e->lay.lds_mlp_bytes : e->lay.lds_bytes;
     hipError_t err = hipLaunchKernel(kern, dim3((unsigned)e->R), dim3(kWave), args, lds, (hipStream_t)stream);
     if (err == hipSuccess) err = hipGetLastError();
@@ -1214,9 +1237,9 @@ extern "C" int prisma_step(prisma_env_t* e, const int32_t* actions, int32_t* obs
     return rc ? rc : auto_reset(e, stream);
 }
 
-// prisma_run (explore_thr null) and prisma_run_explore
+// prisma_run (explore_thr null), prisma_run_explore and prisma_run_explore_smart (action_hist set)
 static int run_fused(prisma_env_t* e, int32_t policy, const void* policy_data, int32_t max_hops,
-                     const uint32_t* explore_thr, void* stream) {
+                     const uint32_t* explore_thr, uint32_t* action_hist, void* stream) {
     if (!e->reset_done) return set_err(PRISMA_ERR_STATE, "prisma_reset must be called first");
     if (policy < PRISMA_POLICY_TABLE || policy > PRISMA_POLICY_DQN_LIGHTER_3 || !policy_data)
         return set_err(PRISMA_ERR_ARG, "policy must be PRISMA_POLICY_TABLE (uint8 table), PRISMA_POLICY_DQN_BUFFER or one "
@@ -1276,7 +1299,9 @@ static int run_fused(prisma_env_t* e, int32_t policy, const void* policy_data, i
     }
     P.max_hops = max_hops;
     P.explore_thr = explore_thr;
-    const void* kern = lightq ? (explore_thr ? e->k_explore_lightq : e->k_lightq)
+    P.action_hist = action_hist;
+    const void* kern = action_hist ? (lightq ? e->k_smart_lightq : P.mode == 4 ? e->k_smart_mlp : e->k_smart)
+                     : lightq ? (explore_thr ? e->k_explore_lightq : e->k_lightq)
                      : explore_thr ? (P.mode == 4 ? e->k_explore_mlp : e->k_explore)
                                    : (P.mode == 4 ? e->k_step_mlp : e->k_step);
     int rc = launch(e, kern, P, stream);
@@ -1289,7 +1314,7 @@ static int run_fused(prisma_env_t* e, int32_t policy, const void* policy_data, i
 
 extern "C" int prisma_run(prisma_env_t* e, int32_t policy, const void* policy_data, int32_t max_hops, void* stream) {
     if (!e) return set_err(PRISMA_ERR_ARG, "null env");
-    return run_fused(e, policy, policy_data, max_hops, nullptr, stream);
+    return run_fused(e, policy, policy_data, max_hops, nullptr, nullptr, stream);
 }
 
 extern "C" int prisma_run_explore(prisma_env_t* e, int32_t policy, const void* policy_data, int32_t max_hops,
@@ -1304,7 +1329,32 @@ extern "C" int prisma_run_explore(prisma_env_t* e, int32_t policy, const void* p
         return set_err(PRISMA_ERR_CONFIG, "prisma_run_explore: this env runs the step kernels with the ctrl paths (train, "
                                           "notify_dest, ns-3 streams, or a tunnelled overlay with log_capacity >= 2^18), "
                                           "which have no exploring instances");
-    return run_fused(e, policy, policy_data, max_hops, explore_thr, stream);
+    return run_fused(e, policy, policy_data, max_hops, explore_thr, nullptr, stream);
+}
+
+extern "C" int prisma_action_history_layout(prisma_env_t* e, int32_t* row_out, int32_t* total_out) {
+    if (!e || !total_out) return set_err(PRISMA_ERR_ARG, "null argument");
+    if (row_out) memcpy(row_out, e->ovrow.data(), sizeof(int32_t) * e->ovrow.size());
+    *total_out = e->ovrow.back();
+    return PRISMA_OK;
+}
+
+extern "C" int prisma_run_explore_smart(prisma_env_t* e, int32_t policy, const void* policy_data, int32_t max_hops,
+                                        const uint32_t* explore_thr, uint32_t* action_hist, uint64_t hist_words,
+                                        void* stream) {
+    if (!e) return set_err(PRISMA_ERR_ARG, "null env");
+    if (!explore_thr) return set_err(PRISMA_ERR_ARG, "explore_thr must be a device uint32 [n_nodes] array");
+    // as the exploring instances: the register-resident engine without the ctrl paths only
+    if (e->lay.mem)
+        return set_err(PRISMA_ERR_CONFIG, "prisma_run_explore_smart: the memory-resident engine has no exploring instances");
+    if (e->kinfo.ctrl || !e->k_smart || !e->k_smart_mlp || !e->k_smart_lightq)
+        return set_err(PRISMA_ERR_CONFIG, "prisma_run_explore_smart: this env runs the step kernels with the ctrl paths "
+                                          "(train, notify_dest, ns-3 streams, or a tunnelled overlay with log_capacity "
+                                          ">= 2^18), which have no exploring instances");
+    if (!action_hist || hist_words != (uint64_t)e->R * (uint64_t)e->ovrow.back())
+        return set_err(PRISMA_ERR_ARG, "prisma_run_explore_smart: action_hist must be a device uint32 [n_replicas][T] "
+                                       "array and hist_words = n_replicas * T (prisma_action_history_layout)");
+    return run_fused(e, policy, policy_data, max_hops, explore_thr, action_hist, stream);
 }
 
 extern "C" int prisma_read_counters(prisma_env_t* e, prisma_counters_t* host_out, void* stream) {

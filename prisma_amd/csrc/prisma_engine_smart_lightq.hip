@@ -1,0 +1,9 @@
+// prisma_engine_smart_lightq.hip -- the register-resident engine's step kernels with the
+// in-kernel reduced DQN-buffer models (engine_core.h lightq_action_reg) and history-weighted
+// exploration (smart_explore_action), without the --train echo / notify_dest code paths
+// (step_kernel.h): prisma_run_explore_smart with PRISMA_POLICY_DQN_LITE ... _DQN_LIGHTER_3.
+#include "step_kernel.h"
+
+const void* prisma_pick_step_smart_lightq(int fs, int ls, bool tun) { return pick_step_smart<true, true>(fs, ls, tun); }
+
+PRISMA_TU_TIMING(prisma_debug_timing_smart_lightq)

@@ -43,50 +43,73 @@ __device__ unsigned long long g_wave_times[4 * 65536];
 #define WT_END() do { } while (0)
 #endif
 
+// The kernel body, shared by the two kernel templates below (EXPL_: 0 greedy, 1 uniform
+// exploration, 2 history-weighted exploration).  A macro rather than an inlined function, for the
+// reason given above, and rather than one more template parameter, so the existing instances keep
+// their symbol names.
+//
+// S.prio_total: 4-wave instances only (at 2 waves per SIMD, config 4's, the same thresholds lost
+// 2 %).
+//
+// An episode that ends with hop budget left (fused run with auto_reset) continues into the next
+// episode from its prebuilt image, in a second inlined copy of the event loop.  A restart inside
+// the first loop would give its clock and sequence numbers a second incoming value each iteration
+// and cost the hot loop ~20 VGPRs (scripts/asm_headline.sh); this copy runs at most once per
+// launch, after which a second episode end stops the replica as before.  The kernel arguments are
+// read again there rather than kept in SGPRs across the first loop, and the stage-out uses the
+// reloaded arguments too: with P's pointers kept live across the second loop the headline instance
+// spilled 7 VGPRs and reloaded them inside it (round 6: 128 VGPRs + 32 B scratch -> 123 VGPRs, no
+// scratch).  The reloaded arguments sit in VGPRs; the smart instances move the history pointer
+// to SGPRs there (two more VGPRs held across the second loop made the headline shape's instance
+// spill 4 VGPRs in that loop's prologue: 20 B scratch, none with the pointer in SGPRs).
+#define PRISMA_STEP_KERNEL_BODY(EXPL_)                                                                  \
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];                                 \
+    const int r = blockIdx.x, lane = threadIdx.x;                                                       \
+    WT_START();                                                                                         \
+    CLayout& LC = *(CLayout*)P.lay;                                                                     \
+    LV lv;                                                                                              \
+    lv.load(P.lay, lane);                                                                               \
+    Regs<FS, LS> R;                                                                                     \
+    stage_in(lds, P, r, lane, R);                                                                       \
+    __syncthreads();                                                                                    \
+    Sim S;                                                                                              \
+    sim_bind(S, lv, lds, P.topo, P.log + (size_t)r * LC.log_cap * LC.rec_bytes, LC.replica_base + (uint32_t)r, lane); \
+    S.tun = TUN;                                                                                        \
+    S.ctrl = CTRL;                                                                                      \
+    if (TUN) S.ring = (uint32_t*)(P.state + (size_t)r * LC.state_bytes + LC.s_ring);   /* HBM FIFOs */  \
+    uint32_t budget = (uint32_t)P.max_hops;                                                             \
+    S.prio_total = StepOcc<FS, LS>::waves >= 4 ? budget : 0u;                                           \
+    const uint32_t done = event_loop<MLP, StepOcc<FS, LS>::mlp_batch, EXPL_, LQ>(P, S, R, r, budget);   \
+    if (P.spare && done < budget) {                                                                     \
+        const KParams* kp = (const KParams*)__builtin_amdgcn_kernarg_segment_ptr();                     \
+        asm volatile("" : "+s"(kp));                                                                    \
+        KParams P2 = *kp;                                                                               \
+        if (EXPL_ == 2) P2.action_hist = rfl_ptr(P2.action_hist);                                       \
+        if (spare_restart(P2, S, R, r, done, budget)) {                                                 \
+            S.prio_base = done;                                                                         \
+            event_loop<MLP, StepOcc<FS, LS>::mlp_batch, EXPL_, LQ>(P2, S, R, r, budget);                \
+            stage_out(lds, P2, r, lane, R);                                                             \
+            WT_END();                                                                                   \
+            return;                                                                                     \
+        }                                                                                               \
+    }                                                                                                   \
+    stage_out(lds, P, r, lane, R);                                                                      \
+    WT_END();
+
 template <int FS, int LS, bool MLP, bool TUN, bool CTRL, bool EXPL = false, bool LQ = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(StepOcc<FS, LS>::waves)))
 prisma_step_kernel_t(KParams P) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    const int r = blockIdx.x, lane = threadIdx.x;
-    WT_START();
-    CLayout& LC = *(CLayout*)P.lay;
-    LV lv;
-    lv.load(P.lay, lane);
-    Regs<FS, LS> R;
-    stage_in(lds, P, r, lane, R);
-    __syncthreads();
-    Sim S;
-    sim_bind(S, lv, lds, P.topo, P.log + (size_t)r * LC.log_cap * LC.rec_bytes, LC.replica_base + (uint32_t)r, lane);
-    S.tun = TUN;
-    S.ctrl = CTRL;
-    if (TUN) S.ring = (uint32_t*)(P.state + (size_t)r * LC.state_bytes + LC.s_ring);   // HBM FIFOs
-    uint32_t budget = (uint32_t)P.max_hops;
-    // (4-wave instances only: at 2 waves per SIMD, config 4's, the same thresholds lost 2 %)
-    S.prio_total = StepOcc<FS, LS>::waves >= 4 ? budget : 0u;
-    const uint32_t done = event_loop<MLP, StepOcc<FS, LS>::mlp_batch, EXPL, LQ>(P, S, R, r, budget);
-    // an episode ended with hop budget left (fused run with auto_reset): the next episode from
-    // its prebuilt image, in a second inlined copy of the event loop.  A restart inside the first
-    // loop would give its clock and sequence numbers a second incoming value each iteration and
-    // cost the hot loop ~20 VGPRs (scripts/asm_headline.sh); this copy runs at most once per
-    // launch, after which a second episode end stops the replica as before.
-    if (P.spare && done < budget) {
-        // the kernel arguments are read again here rather than kept in SGPRs across the first loop
-        const KParams* kp = (const KParams*)__builtin_amdgcn_kernarg_segment_ptr();
-        asm volatile("" : "+s"(kp));
-        const KParams P2 = *kp;
-        if (spare_restart(P2, S, R, r, done, budget)) {
-            S.prio_base = done;
-            event_loop<MLP, StepOcc<FS, LS>::mlp_batch, EXPL, LQ>(P2, S, R, r, budget);
-            // stage out from the reloaded arguments too: with P's pointers kept live across this
-            // loop the headline instance spilled 7 VGPRs and reloaded them inside it (round 6:
-            // 128 VGPRs + 32 B scratch -> 123 VGPRs, no scratch)
-            stage_out(lds, P2, r, lane, R);
-            WT_END();
-            return;
-        }
-    }
-    stage_out(lds, P, r, lane, R);
-    WT_END();
+    PRISMA_STEP_KERNEL_BODY(EXPL ? 1 : 0)
+}
+
+// SMART: the instances with history-weighted exploration (engine_core.h smart_explore_action;
+// prisma_run_explore_smart), without the ctrl paths -- sets of their own once more, beside the
+// exploring ones
+template <int FS, int LS, bool MLP, bool TUN, bool LQ>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(StepOcc<FS, LS>::waves)))
+prisma_step_kernel_smart_t(KParams P) {
+    constexpr bool CTRL = false;
+    PRISMA_STEP_KERNEL_BODY(2)
 }
 
 // instantiations: flow slots FS in {1,2,4,8} (F <= 512), link slots LS in {1,2,4} (L <= 256)
@@ -102,7 +125,8 @@ template <int FS, int LS, bool CTRL, bool MLP, bool EXPL = false, bool LQ = fals
 // prisma_engine.hip (CTRL, tables), prisma_engine_mlp.hip (CTRL, MLP), prisma_engine_lite.hip
 // and prisma_engine_lite_mlp.hip (without the ctrl paths), prisma_engine_explore.hip and
 // prisma_engine_explore_mlp.hip (EXPL, without the ctrl paths), prisma_engine_lightq.hip and
-// prisma_engine_explore_lightq.hip (LQ, without the ctrl paths)
+// prisma_engine_explore_lightq.hip (LQ, without the ctrl paths), prisma_engine_smart.hip,
+// prisma_engine_smart_mlp.hip and prisma_engine_smart_lightq.hip (SMART, without the ctrl paths)
 template <bool CTRL, bool MLP, bool EXPL = false, bool LQ = false>
 static const void* pick_step(int fs, int ls, bool tun) {
 #ifdef PRISMA_DEV_HEADLINE
@@ -111,6 +135,21 @@ static const void* pick_step(int fs, int ls, bool tun) {
                                                          : nullptr;
 #else
 #define PK(F_, L_) if (fs == F_ && ls == L_) return step_kernel<F_, L_, CTRL, MLP, EXPL, LQ>(tun);
+    PK(1, 1) PK(1, 2) PK(1, 4) PK(2, 1) PK(2, 2) PK(2, 4) PK(4, 1) PK(4, 2) PK(4, 4) PK(8, 1) PK(8, 2) PK(8, 4)
+#undef PK
+    return nullptr;
+#endif
+}
+
+template <bool MLP, bool LQ = false>
+static const void* pick_step_smart(int fs, int ls, bool tun) {
+#ifdef PRISMA_DEV_HEADLINE
+    return nullptr;
+#else
+#define PK(F_, L_)                                                                                      \
+    if (fs == F_ && ls == L_)                                                                           \
+        return tun ? (const void*)prisma_step_kernel_smart_t<F_, L_, MLP, true, LQ>                     \
+                   : (const void*)prisma_step_kernel_smart_t<F_, L_, MLP, false, LQ>;
     PK(1, 1) PK(1, 2) PK(1, 4) PK(2, 1) PK(2, 2) PK(2, 4) PK(4, 1) PK(4, 2) PK(4, 4) PK(8, 1) PK(8, 2) PK(8, 4)
 #undef PK
     return nullptr;

@@ -97,7 +97,7 @@ class _Plan(C.Structure):
 
 EXPORTS = [
     "prisma_abi_version", "prisma_last_error", "prisma_build_id", "prisma_create", "prisma_reset", "prisma_step", "prisma_run",
-    "prisma_run_explore",
+    "prisma_run_explore", "prisma_action_history_layout", "prisma_run_explore_smart",
     "prisma_read_counters", "prisma_counters_device", "prisma_log_view", "prisma_copy_log",
     "prisma_copy_counters", "prisma_gather_records", "prisma_state_bytes", "prisma_plan", "prisma_destroy",
     "prisma_compact_pending", "prisma_expand_actions", "prisma_kernel_info",
@@ -143,6 +143,11 @@ def load_library(path: str = None):
     L.prisma_run.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
     L.prisma_run_explore.restype = C.c_int
     L.prisma_run_explore.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.prisma_action_history_layout.restype = C.c_int
+    L.prisma_action_history_layout.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+    L.prisma_run_explore_smart.restype = C.c_int
+    L.prisma_run_explore_smart.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                           C.c_uint64, C.c_void_p]
     L.prisma_read_counters.restype = C.c_int
     L.prisma_read_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.prisma_counters_device.restype = C.c_int
@@ -349,7 +354,23 @@ class PrismaEngine:
                                           out.data_ptr(), _stream_handle(stream)))
         return out
 
-    def run(self, policy, max_hops: int, stream=None, explore=None, model: str = "buffer"):
+    def action_history_layout(self):
+        """prisma_action_history_layout: (row int32 [n_nodes + 1], T) -- node v's actions are
+        columns row[v] .. row[v + 1] of an action history, by underlay id (empty for a node outside
+        the overlay); T = row[n_nodes] is the sum of the overlay degrees."""
+        row = np.zeros(self.topo.n_nodes + 1, dtype=np.int32)
+        total = C.c_int32()
+        _check(_lib.prisma_action_history_layout(self.h, row.ctypes.data, C.byref(total)))
+        return row, int(total.value)
+
+    def new_action_history(self, fill: int = 1):
+        """A device int32 [n_replicas, T] action history for run(..., action_history=), every count
+        `fill` (the reference starts at ones).  The kernels read its bits as uint32."""
+        import torch
+        _, total = self.action_history_layout()
+        return torch.full((self.R, total), int(fill), dtype=torch.int32, device=self.torch_device)
+
+    def run(self, policy, max_hops: int, stream=None, explore=None, model: str = "buffer", action_history=None):
         """Fused in-kernel policy: every replica executes up to max_hops hops.
 
         policy: a device uint8 [N, N] action table (SP, DQ-routing argmin), or the device fp32
@@ -363,9 +384,24 @@ class PrismaEngine:
         explore: None (greedy), or the epsilons of an epsilon-greedy rollout (prisma_run_explore;
         prisma_amd/explore.py restates its draw rule): a scalar, or a float tensor / array
         [n_nodes] indexed by underlay node id. Constant over the launch; a device tensor is
-        converted on the device without a host sync."""
+        converted on the device without a host sync.
+
+        action_history: None, or with `explore` the history-weighted ("smart") exploration of
+        prisma_run_explore_smart: a contiguous int32 [n_replicas, T] tensor on this engine's device
+        (new_action_history), which the launch reads and updates in place -- an exploring decision
+        picks by its node's counts instead of uniformly, and every data decision counts its action
+        (explore.py restates the rule).  The caller owns it and carries it between launches."""
         import torch
         n, d = self.topo.n_nodes, self.topo.max_deg
+        if action_history is not None:
+            if explore is None:
+                raise PrismaError("prisma_run_explore_smart: action_history needs explore (the epsilons)")
+            total = self.action_history_layout()[1]
+            if (not torch.is_tensor(action_history) or action_history.device != self.torch_device
+                    or action_history.dtype != torch.int32 or tuple(action_history.shape) != (self.R, total)
+                    or not action_history.is_contiguous()):
+                raise PrismaError(f"prisma_run_explore_smart: action_history must be a contiguous int32 "
+                                  f"[{self.R}, {total}] tensor on {self.torch_device} (new_action_history)")
         if not policy.is_cuda:
             raise PrismaError("policy data must live on the device")
         if model not in MODEL_POLICIES:
@@ -385,6 +421,11 @@ class PrismaEngine:
             return
         with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
             self._thr_keep = self._explore_thr(explore)
+        if action_history is not None:
+            _check(_lib.prisma_run_explore_smart(self.h, kind, self._policy_keep.data_ptr(), int(max_hops),
+                                                 self._thr_keep.data_ptr(), action_history.data_ptr(),
+                                                 action_history.numel(), _stream_handle(stream)))
+            return
         _check(_lib.prisma_run_explore(self.h, kind, self._policy_keep.data_ptr(), int(max_hops),
                                        self._thr_keep.data_ptr(), _stream_handle(stream)))
 

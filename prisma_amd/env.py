@@ -140,10 +140,10 @@ class VecRoutingEnv:
                 "error": cf["error"]}
         return reward, done, info
 
-    def run(self, table: torch.Tensor, max_hops: int, explore=None, model: str = "buffer"):
+    def run(self, table: torch.Tensor, max_hops: int, explore=None, model: str = "buffer", action_history=None):
         """Fused launch (PrismaEngine.run); explore: epsilons of an epsilon-greedy rollout;
         model: the kind of a packed fp32 policy."""
-        self.engine.run(table, max_hops, explore=explore, model=model)
+        self.engine.run(table, max_hops, explore=explore, model=model, action_history=action_history)
 
     def counters(self) -> np.ndarray:
         return self.engine.counters()

@@ -268,7 +268,8 @@ class QRoutingTrainer:
                  big_signaling_size: int = 512, packet_size: int = 512, pending_cap: int = 1 << 20,
                  n_replicas: int = 1, signaling_sim: int = 1, sync_step: float = 1.0, sync_ratio: float = 0.1,
                  link_cap: int = 500000, link_delay_ms: float = 1.0, prioritized_replay: bool = False,
-                 max_snapshots: Optional[int] = None, warn_stored_bytes: Optional[int] = 1 << 30):
+                 max_snapshots: Optional[int] = None, warn_stored_bytes: Optional[int] = 1 << 30,
+                 smart_exploration: bool = False):
         if signaling_type not in ("ideal", "NN", "target"):
             raise ValueError("signaling_type must be 'ideal', 'NN' or 'target'")
         self.topo = topo
@@ -302,6 +303,15 @@ class QRoutingTrainer:
         self.explore = LinearSchedule(iteration_num, eps_initial, eps_final)
         self.transitions_seen = torch.zeros(N, dtype=torch.int64, device=self.device)
         self.gen = torch.Generator(device=self.device).manual_seed(int(seed) + 1)
+        # --smart_exploration (argument_parser.py:76; forwarder.py:125-127, 171-189): an exploring agent
+        # picks action a with probability proportional to 1 - history[a] / sum(history), history being
+        # the node's count of the actions it has taken, from ones.  One history per (replica, node):
+        # int32 [R, T], node v's actions in columns hist_row[v] .. hist_row[v + 1] -- the layout of
+        # PrismaEngine.action_history_layout(), whose fused launches update it in place (train_fused)
+        self.smart_exploration = bool(smart_exploration)
+        self.hist_row = torch.from_numpy(np.concatenate([[0], np.cumsum(topo.degrees.astype(np.int64))])).to(self.device)
+        self.action_history = (torch.ones((int(n_replicas), int(self.hist_row[-1])), dtype=torch.int32,
+                                          device=self.device) if self.smart_exploration else None)
         # ---- signalling (module docstring) ----
         self.signaling = signaling_type
         self.signaling_sim = int(signaling_sim)
@@ -390,7 +400,13 @@ class QRoutingTrainer:
     # -- acting ---------------------------------------------------------------
     @torch.no_grad()
     def act(self, obs: torch.Tensor, node: torch.Tensor, explore: bool = True) -> torch.Tensor:
-        """argmin_a Q (learner.py:142-159), epsilon-greedy per the deciding node's schedule."""
+        """argmin_a Q (learner.py:142-159), epsilon-greedy per the deciding node's schedule.
+
+        With smart_exploration the exploring pick is weighted by the action history instead of
+        uniform (the rule of prisma_amd/explore.py with this generator's draws in place of the
+        Philox words), and the action of every replica whose pending notification is a data
+        decision is counted, explored or not; obs and node then hold one row per replica."""
+        valid = node.long() >= 0
         node = node.long().clamp_min(0)
         ctrl = obs[:, 0] == 1000                       # control notification: the action is ignored
         if bool(ctrl.any()):
@@ -402,8 +418,34 @@ class QRoutingTrainer:
             r = torch.rand(node.shape, generator=self.gen, device=self.device, dtype=torch.float64)
             ra = (torch.rand(node.shape, generator=self.gen, device=self.device, dtype=torch.float64)
                   * self.deg[node].clamp_min(1)).long()
+            if self.smart_exploration:
+                ra = self._smart_pick(node, ra)
             a = torch.where(r < eps, ra, a)
+        if self.smart_exploration:
+            if node.shape[0] != self.R:
+                raise ValueError("smart_exploration: act() needs one notification per replica")
+            count = valid & ~ctrl & (a >= 0) & (a < self.deg[node])
+            rows = torch.nonzero(count).squeeze(1)
+            # (one row per replica: no two updates share an element)
+            self.action_history[rows, self.hist_row[node[rows]] + a[rows]] += 1
         return a.to(torch.int32)
+
+    def _smart_pick(self, node: torch.Tensor, uniform: torch.Tensor) -> torch.Tensor:
+        """The history-weighted pick of every row's replica at its node: the first action whose
+        prefix of weights w_i = nb - h_i exceeds a uniform draw in [0, W), W = (deg - 1) nb; the
+        uniform pick where W = 0 (degree 1, a row of zeros)."""
+        deg = self.deg[node]
+        j = torch.arange(self.D, device=self.device)
+        inrow = j[None, :] < deg[:, None]
+        col = (self.hist_row[node][:, None] + j[None, :]).clamp_max(self.action_history.shape[1] - 1)
+        rep = torch.arange(node.shape[0], device=self.device)[:, None]
+        h = (self.action_history[rep, col].long() & 0xFFFFFFFF).double() * inrow      # (the bits are uint32 counts)
+        nb = h.sum(1, keepdim=True)
+        prefix = torch.cumsum((nb - h) * inrow, 1)
+        W = prefix[:, -1]
+        u = torch.rand(node.shape, generator=self.gen, device=self.device, dtype=torch.float64) * W
+        pick = (prefix <= u[:, None]).sum(1).clamp_max((deg - 1).clamp_min(0))
+        return torch.where(W > 0, pick, uniform)
 
     def explore_eps(self) -> torch.Tensor:
         """Every node's epsilon now (device float64 [N], by underlay id): the LinearSchedule value
@@ -779,7 +821,10 @@ class QRoutingTrainer:
                 "stored_generations": len(self._gen_w), "stale_syncs": int(self.stale_syncs),
                 "stored_bytes": len(self._gen_w) * self.generation_bytes,
                 "peak_generations": int(self.peak_generations),
-                "peak_stored_bytes": int(self.peak_generations) * self.generation_bytes}
+                "peak_stored_bytes": int(self.peak_generations) * self.generation_bytes,
+                # every count of the smart-exploration history (R * T ones + the decisions counted), 0 without
+                "action_history_total": (int((self.action_history.long() & 0xFFFFFFFF).sum())
+                                         if self.action_history is not None else 0)}
 
     def weights_of(self, version: int) -> dict:
         """The stacked online weights copy `version` refers to."""
@@ -837,6 +882,9 @@ def train_fused(env, trainer: QRoutingTrainer, launches: int, hops_per_launch: i
     transitions enter the buffers, the due syncs run, and every ``train_every`` launches a training
     step.  Returns the mean losses of the training steps.
 
+    With QRoutingTrainer(smart_exploration=True) every launch explores by the trainer's action
+    history and counts into it (run(..., action_history=trainer.action_history)).
+
     "ideal" signalling only (a transition enters the buffer when it completes; the others wait for
     signalling packets the fused rollout does not hand out).  A launch that writes more records
     than the env's log ring holds would lose transitions silently: RuntimeError; size
@@ -852,11 +900,12 @@ def train_fused(env, trainer: QRoutingTrainer, launches: int, hops_per_launch: i
     trainer.advance_clock(info["now_ns"], info.get("episode"))
     cap = env.engine.log_capacity
     losses = []
+    smart = {"action_history": trainer.action_history} if trainer.smart_exploration else {}
     for k in range(launches):
         if trainer.kind == "routing":
-            env.run(trainer.q.argmin_table(), hops_per_launch, explore=trainer.explore_eps())
+            env.run(trainer.q.argmin_table(), hops_per_launch, explore=trainer.explore_eps(), **smart)
         else:
-            env.run(trainer.q.pack(), hops_per_launch, explore=trainer.explore_eps(), model=trainer.kind)
+            env.run(trainer.q.pack(), hops_per_launch, explore=trainer.explore_eps(), model=trainer.kind, **smart)
         cf = env._counter_fields()
         # one host read: replicas over the log's size, and replicas per PRISMA_EBIT_* bit
         over, *per_bit = torch.stack([((cf["dec_count"] - env._consumed) >= cap).sum()]

@@ -8,8 +8,10 @@
   b  trainer.train_fused(): one fused epsilon-greedy launch of --hops hops per replica, then the
      launch's transitions into the buffers -- the same two figures
   c  PrismaEngine.run(..., explore=0.1) alone against run() alone, hops/s (the cost of the draw)
+  d  PrismaEngine.run(..., explore=0.1, action_history=...) alone against run(..., explore=0.1)
+     alone, hops/s (the cost of the action counts and the history-weighted pick)
 
-    python scripts/rollout_bench.py --part a        # or b, c; --repeat 2 prints each line twice
+    python scripts/rollout_bench.py --part a        # or b, c, d; --repeat 2 prints each line twice
 
 Every part warms up first and is timed between device synchronisations.  bench.py stays the
 headline's yardstick; this script only compares the rollout paths with each other."""
@@ -116,9 +118,36 @@ def part_c(args):
     env.close()
 
 
+def part_d(args):
+    env, tr = make(args, 8192)
+    table = tr.q.argmin_table()
+    eps = torch.full((env.topo.n_nodes,), args.eps, dtype=torch.float64, device=env.device)
+    for _ in range(args.repeat):
+        res = {}
+        for name in ("explore", "smart"):
+            kw = {"explore": eps}
+            if name == "smart":
+                kw["action_history"] = env.engine.new_action_history()
+            env.engine.reset(0)
+            for _ in range(args.warmup_launches):
+                env.run(table, args.hops, **kw)
+            torch.cuda.synchronize()
+            h0 = int(env.counters()["hops_total"].sum())
+            dt, _ = wall(lambda: [env.run(table, args.hops, **kw) for _ in range(args.launches)])
+            cnt = env.counters()
+            assert int(cnt["error"].max()) == 0
+            res[name] = (int(cnt["hops_total"].sum()) - h0) / dt
+        out = common(args, "d")
+        out.update(path="run alone", launches=args.launches, hops_per_launch=args.hops,
+                   explore_hops_per_s=round(res["explore"], 1), smart_hops_per_s=round(res["smart"], 1),
+                   smart_over_explore=round(res["smart"] / res["explore"], 4))
+        print(json.dumps(out), flush=True)
+    env.close()
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument("--part", choices=["a", "b", "c"], required=True)
+    p.add_argument("--part", choices=["a", "b", "c", "d"], required=True)
     p.add_argument("--topology", default="abilene")
     p.add_argument("--replicas", type=int, default=4096)
     p.add_argument("--eps", type=float, default=0.1)
@@ -130,7 +159,7 @@ def main(argv=None):
     p.add_argument("--warmup-steps", type=int, default=20)
     p.add_argument("--repeat", type=int, default=2, help="timed repeats, one JSON line each (the spread)")
     args = p.parse_args(argv)
-    {"a": part_a, "b": part_b, "c": part_c}[args.part](args)
+    {"a": part_a, "b": part_b, "c": part_c, "d": part_d}[args.part](args)
 
 
 if __name__ == "__main__":
