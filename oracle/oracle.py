@@ -220,10 +220,12 @@ class OracleSim:
         return out[0]
 
     def diag(self) -> dict:
-        """Test diagnostics (or_diag): drops inside tunnels, FIFO depths now."""
-        out = np.zeros(4, dtype=np.int64)
+        """Test diagnostics (or_diag): drops inside tunnels, FIFO depths now, and over the run so
+        far the most packets at once on one switch link's wire and in one switch link's ring."""
+        out = np.zeros(6, dtype=np.int64)
         lib().or_diag(self.h, out.ctypes.data)
-        return dict(relay_drops=int(out[0]), max_queue=int(out[1]), queued=int(out[2]), deep_fifos=int(out[3]))
+        return dict(relay_drops=int(out[0]), max_queue=int(out[1]), queued=int(out[2]), deep_fifos=int(out[3]),
+                    max_wire=int(out[4]), peak_ring=int(out[5]))
 
     def enable_trace(self, on: bool = True):
         lib().or_enable_trace(self.h, int(on))

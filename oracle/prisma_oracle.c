@@ -156,6 +156,7 @@ typedef struct {              /* PointToPointNetDevice + DropTailQueue   */
     uint32_t max_bytes;       /* byte mode if > 0                       */
     uint32_t max_pkts;        /* packet mode otherwise                  */
     int from_node, to_node, is_access;
+    int wire;                 /* or_diag: packets between transmit_start and their receive */
 } netdev_t;
 
 typedef struct { uint32_t idx; uint64_t ms; } sent_t;
@@ -287,6 +288,9 @@ struct or_sim {
     char info[4096];
     /* test diagnostics (or_diag): data packets dropped on a FIFO inside a tunnel */
     int64_t relay_drops;
+    /* the most packets at once between transmit_start and their channel receive on one switch
+     * link (max_wire), and the most queued + on the wire there (peak_ring: what a ring holds) */
+    int64_t max_wire, peak_ring;
 };
 
 static void* xrealloc(void* p, size_t n) {
@@ -418,6 +422,7 @@ static void transmit_start(or_sim_t* s, int di, int p) {            /* :273-302 
     int64_t tx = tx_time(d, s->pk[p].size);
     schedule(s, s->now + tx, EV_COMPLETE, di, -1);                   /* :295 */
     schedule(s, s->now + tx + d->delay, EV_RECEIVE, di, p);           /* :296 (channel) */
+    if (++d->wire > s->max_wire && !d->is_access) s->max_wire = d->wire;
 }
 
 static void transmit_complete(or_sim_t* s, int di) {                /* :305-336 */
@@ -457,6 +462,7 @@ static int dev_send(or_sim_t* s, int di, int p) {                   /* :595-666 
     if (ok) {
         q_push(d, p);
         d->nbytes += k->size;
+        if (!d->is_access && d->q_len + d->wire > s->peak_ring) s->peak_ring = d->q_len + d->wire;
         if (!d->busy) {                                              /* :643-650 */
             int h = q_pop(d);
             d->nbytes -= s->pk[h].size;
@@ -960,6 +966,7 @@ static int run_until_decision(or_sim_t* s) {
         case EV_BSEND: bsig_send_packet(s, e.id); break;
         case EV_COMPLETE: transmit_complete(s, e.id); break;
         case EV_RECEIVE:
+            s->dev[e.id].wire--;
             if (receive(s, e.id, e.pkt)) return 1;
             break;
         }
@@ -1259,7 +1266,7 @@ void or_counters(const or_sim_t* s, void* out) {
     memcpy(out, &c, sizeof(c));
 }
 
-void or_diag(const or_sim_t* s, int64_t out[4]) {
+void or_diag(const or_sim_t* s, int64_t out[6]) {
     int64_t mx = 0, tot = 0, deep = 0;
     for (int i = 0; i < s->E; ++i) {               /* switch devices: the FIFOs a test probes */
         const int n = s->dev[i].q_len;
@@ -1271,6 +1278,8 @@ void or_diag(const or_sim_t* s, int64_t out[4]) {
     out[1] = mx;
     out[2] = tot;
     out[3] = deep;
+    out[4] = s->max_wire;
+    out[5] = s->peak_ring;
 }
 
 void or_enable_trace(or_sim_t* s, int on) { s->trace_on = on; }

@@ -115,8 +115,11 @@ void or_counters(const or_sim_t* s, void* out);
 /* Test diagnostics: out[0] data packets dropped on a FIFO inside a tunnel (not the deciding
  * node's first link), out[1] the longest switch FIFO now (packets waiting, excluding the one in
  * transmission), out[2] packets waiting in all switch FIFOs, out[3] switch FIFOs with more than
- * 4 waiting (deeper than the engine's LDS FIFO window, so part of them sits in the HBM ring). */
-void or_diag(const or_sim_t* s, int64_t out[4]);
+ * 4 waiting (deeper than the engine's LDS FIFO window, so part of them sits in the HBM ring),
+ * out[4] the most packets that were at once between transmit_start and their channel receive on
+ * one switch link (the one in transmission included: the engine's wire slots), out[5] the most
+ * that were at once waiting or on the wire of one switch link (the entries its ring holds). */
+void or_diag(const or_sim_t* s, int64_t out[6]);
 
 /* Optional event trace: (t_ns, seq, kind, id) per executed event. */
 void    or_enable_trace(or_sim_t* s, int on);
