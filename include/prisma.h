@@ -470,6 +470,64 @@ int prisma_copy_counters(prisma_env_t* env, void* dst_device, void* stream);
 int prisma_gather_records(prisma_env_t* env, const int32_t* replica, const uint32_t* dec,
                           int32_t n, void* dst_device, void* stream);
 
+/*
+ * Per-node replay rings of a trainer (prisma_ingest_transitions): one FIFO ring of `size`
+ * transitions per node (replay_buffer.py:29-37), as contiguous device arrays in the layouts of
+ * prisma_amd.trainer.ReplayBuffers; N = n_nodes, W = obs_width, rows by underlay node id.
+ */
+typedef struct prisma_replay {
+    int32_t* obs;               /* [N][size][W]                            */
+    int32_t* next_obs;          /* [N][size][W]                            */
+    int64_t* action;            /* [N][size]                               */
+    float*   reward;            /* [N][size]                               */
+    uint8_t* done;              /* [N][size], 0 / 1                        */
+    int64_t* replica;           /* [N][size]: the replica an item came from */
+    int64_t* next_idx;          /* [N]: the slot the node's next item takes */
+    int64_t* count;             /* [N]: items in the ring, <= size         */
+    int64_t* total;             /* [N]: items ever added                   */
+    int64_t  size;
+    int32_t  n_nodes;
+    int32_t  obs_width;
+} prisma_replay_t;
+
+/*
+ * The replay transitions completed since the previous call, from the decision log straight into
+ * the rings: three launches on `stream`, no host read, no atomic deciding a slot (placement
+ * follows from prefix sums, so the result is deterministic).  It has exactly the effect of
+ * VecRoutingEnv.transitions() followed by ReplayBuffers.add() on a non-prioritized buffer,
+ * together with the update of the caller's progress mark: consumed, device int64 [n_replicas],
+ * the index of each replica's first record not yet turned into transitions (zeros after a reset).
+ *
+ * The rule per replica r, with dec its dec_count and cap = log_capacity:
+ *   Window.    The new records are d in [lo, dec), lo = max(consumed[r], dec - cap + 1).  A
+ *              record is final if its status is not PRISMA_ST_PENDING.
+ *   Consumed.  If the window is non-empty, consumed[r] = dec - (1 if the window's last record
+ *              is pending else 0); otherwise consumed[r] is unchanged.
+ *   Hop item.  A final record d with prev >= 0 yields (obs_p, action_p, (float)reward_d, obs_d,
+ *              status_d == PRISMA_ST_DESTINATION, node_p, r), p being the record at slot
+ *              prev mod cap of the same replica.
+ *   Loss item. A final record d with status PRISMA_ST_DROPPED yields (obs_d, action_d,
+ *              (float)loss_penalty, [obs_d[0], 0, ...], true, node_d, r).
+ *   Batch order.  All hop items first, in (r, d) ascending order; all loss items follow, in
+ *              (r, d) ascending order.
+ *   Rank.      Within that order, an item's rank among the items of its node u gives slot
+ *              (next_idx[u] + rank) mod size.
+ *   Overflow.  An item is written only if rank >= count_u - size, count_u being the node's items
+ *              in this call: an overflowing batch keeps its last `size` items.
+ *   Ring counters.  Afterwards next_idx[u] = (next_idx[u] + count_u) mod size, count[u] =
+ *              min(count[u] + count_u, size), total[u] += count_u.
+ *   Field encoding.  The action is the record's sign-extended int8; the reward conversion is
+ *              round-to-nearest-even.
+ * An item whose node id is >= n_nodes is skipped in every pass (the engines write none).
+ * Either engine's log.  Null env, consumed, rings or ring pointer, size < 1, or rings->obs_width /
+ * rings->n_nodes different from the env's: PRISMA_ERR_ARG, nothing is launched.  The per-(replica,
+ * node) counts and offsets live in library-owned scratch, allocated at the first call and freed
+ * by prisma_destroy; calls on one env are ordered by their stream.  (Added without an ABI
+ * version change: no struct or signature moved.)
+ */
+int prisma_ingest_transitions(prisma_env_t* env, int64_t* consumed, const prisma_replay_t* rings,
+                              void* stream);
+
 /* Active-replica compaction (ABI 9) for a batched external policy, which then
  * evaluates only the replicas with a pending decision -- the reference's
  * Forwarder steps only the nodes that were notified (ns3env.py:417-423,

@@ -346,6 +346,7 @@ struct prisma_env {
     uint32_t* d_rng = nullptr;           // ns-3 stream table (PRISMA_RNG_NS3, engine_layout.h kMrgPowers)
     prisma_kernel_info_t kinfo{};        // the step-kernel instances prisma_create picked
     bool reset_done = false;
+    void* d_ingest = nullptr;            // prisma_ingest_transitions' counts and offsets (first use)
 };
 
 static thread_local std::string g_err;
@@ -1431,6 +1432,34 @@ extern "C" int prisma_compact_pending(prisma_env_t* e, const uint8_t* mask, cons
     return PRISMA_OK;
 }
 
+// the replay-ring ingest kernels (prisma_engine_ingest.hip)
+size_t prisma_ingest_scratch_bytes(int32_t R, int32_t N);
+hipError_t prisma_ingest_launch(const unsigned char* log, const prisma_counters_t* cnt, int64_t* consumed, int32_t R,
+                                int32_t N, int32_t W, uint32_t cap, uint32_t rec_bytes, float loss_penalty,
+                                void* scratch, const prisma_replay_t* rings, hipStream_t stream);
+
+extern "C" int prisma_ingest_transitions(prisma_env_t* e, int64_t* consumed, const prisma_replay_t* rings,
+                                         void* stream) {
+    if (!e || !consumed || !rings) return set_err(PRISMA_ERR_ARG, "null argument (env, consumed and rings are required)");
+    if (!rings->obs || !rings->next_obs || !rings->action || !rings->reward || !rings->done || !rings->replica ||
+        !rings->next_idx || !rings->count || !rings->total)
+        return set_err(PRISMA_ERR_ARG, "prisma_ingest_transitions: null ring pointer");
+    if (rings->size < 1) return set_err(PRISMA_ERR_ARG, "prisma_ingest_transitions: ring size must be >= 1");
+    if (rings->obs_width != e->lay.W || rings->n_nodes != e->lay.N)
+        return set_err(PRISMA_ERR_ARG, "prisma_ingest_transitions: the rings' obs_width = " +
+                                       std::to_string(rings->obs_width) + " / n_nodes = " +
+                                       std::to_string(rings->n_nodes) + " differ from the env's " +
+                                       std::to_string(e->lay.W) + " / " + std::to_string(e->lay.N));
+    (void)hipSetDevice(e->device);
+    if (!e->d_ingest && !HIP_OK(hipMalloc(&e->d_ingest, prisma_ingest_scratch_bytes(e->R, e->lay.N))))
+        return set_err(PRISMA_ERR_NOMEM, "hipMalloc failed (ingest scratch)");
+    hipError_t err = prisma_ingest_launch(e->d_log, e->d_cnt, consumed, e->R, e->lay.N, e->lay.W, e->lay.log_cap,
+                                          e->lay.rec_bytes, e->lay.loss_penalty_f, e->d_ingest, rings,
+                                          (hipStream_t)stream);
+    if (err != hipSuccess) return set_err(PRISMA_ERR_LAUNCH, std::string("ingest launch failed: ") + hipGetErrorString(err));
+    return PRISMA_OK;
+}
+
 extern "C" int prisma_expand_actions(prisma_env_t* e, const int32_t* ids, const int32_t* count,
                                      const int32_t* packed_actions, int32_t fill, int32_t* actions_out, void* stream) {
     if (!e || !ids || !count || !packed_actions || !actions_out) return set_err(PRISMA_ERR_ARG, "null argument");
@@ -1485,5 +1514,6 @@ extern "C" void prisma_destroy(prisma_env_t* e) {
     if (e->d_lq_rp) (void)hipFree(e->d_lq_rp);
     if (e->d_spare) (void)hipFree(e->d_spare);
     if (e->d_rng) (void)hipFree(e->d_rng);
+    if (e->d_ingest) (void)hipFree(e->d_ingest);
     delete e;
 }

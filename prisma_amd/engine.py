@@ -89,6 +89,13 @@ class _KernelInfo(C.Structure):
                 ("relay_dec_bits", C.c_uint32)]
 
 
+class _Replay(C.Structure):
+    """prisma_replay_t: the per-node replay rings prisma_ingest_transitions writes."""
+    _fields_ = [("obs", C.c_void_p), ("next_obs", C.c_void_p), ("action", C.c_void_p), ("reward", C.c_void_p),
+                ("done", C.c_void_p), ("replica", C.c_void_p), ("next_idx", C.c_void_p), ("count", C.c_void_p),
+                ("total", C.c_void_p), ("size", C.c_int64), ("n_nodes", C.c_int32), ("obs_width", C.c_int32)]
+
+
 class _Plan(C.Structure):
     _fields_ = [("state_bytes", C.c_uint32), ("lds_bytes", C.c_uint32), ("lds_state_bytes", C.c_uint32),
                 ("ring_entries", C.c_uint32), ("record_bytes", C.c_uint32), ("obs_width", C.c_int32),
@@ -100,7 +107,7 @@ EXPORTS = [
     "prisma_run_explore", "prisma_action_history_layout", "prisma_run_explore_smart",
     "prisma_read_counters", "prisma_counters_device", "prisma_log_view", "prisma_copy_log",
     "prisma_copy_counters", "prisma_gather_records", "prisma_state_bytes", "prisma_plan", "prisma_destroy",
-    "prisma_compact_pending", "prisma_expand_actions", "prisma_kernel_info",
+    "prisma_compact_pending", "prisma_expand_actions", "prisma_kernel_info", "prisma_ingest_transitions",
 ]
 
 _lib = None
@@ -165,6 +172,8 @@ def load_library(path: str = None):
     L.prisma_expand_actions.restype = C.c_int
     L.prisma_expand_actions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                         C.c_void_p]
+    L.prisma_ingest_transitions.restype = C.c_int
+    L.prisma_ingest_transitions.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_Replay), C.c_void_p]
     L.prisma_kernel_info.restype = C.c_int
     L.prisma_kernel_info.argtypes = [C.c_void_p, C.POINTER(_KernelInfo)]
     L.prisma_state_bytes.restype = C.c_int
@@ -471,6 +480,34 @@ class PrismaEngine:
             _check(_lib.prisma_gather_records(self.h, rep.data_ptr(), d.data_ptr(), n, out.data_ptr(),
                                               _stream_handle(stream)))
         return out[:n]
+
+    def ingest_transitions(self, consumed, buffers, stream=None):
+        """prisma_ingest_transitions: the transitions completed since `consumed` (device int64
+        [n_replicas], each replica's first record not yet ingested; advanced in place) from the
+        decision log straight into `buffers` (a non-prioritized trainer.ReplayBuffers on this
+        engine's device), exactly as ``buffers.add(env.transitions())`` would -- the order rule is
+        in include/prisma.h.  Three launches on torch's current stream (or `stream`), no host read."""
+        import torch
+        if getattr(buffers, "prioritized", False):
+            raise ValueError("prisma_ingest_transitions fills a non-prioritized ReplayBuffers (priorities are "
+                             "kept by ReplayBuffers.add)")
+        want = [("consumed", consumed, torch.int64, (self.R,))]
+        n, size, w = int(buffers.N), int(buffers.size), int(buffers.W)
+        for name, dt, shape in (("obs", torch.int32, (n, size, w)), ("next_obs", torch.int32, (n, size, w)),
+                                ("action", torch.int64, (n, size)), ("reward", torch.float32, (n, size)),
+                                ("done", torch.bool, (n, size)), ("replica", torch.int64, (n, size)),
+                                ("next_idx", torch.int64, (n,)), ("count", torch.int64, (n,)),
+                                ("total", torch.int64, (n,))):
+            want.append((name, getattr(buffers, name), dt, shape))
+        for name, t, dt, shape in want:
+            if (not torch.is_tensor(t) or t.device != self.torch_device or t.dtype != dt or tuple(t.shape) != shape
+                    or not t.is_contiguous()):
+                raise ValueError(f"prisma_ingest_transitions: {name} must be a contiguous {dt} tensor of shape "
+                                 f"{shape} on {self.torch_device}")
+        rings = _Replay(*[getattr(buffers, k).data_ptr() for k in ("obs", "next_obs", "action", "reward", "done",
+                                                                   "replica", "next_idx", "count", "total")],
+                        size, n, w)
+        _check(_lib.prisma_ingest_transitions(self.h, consumed.data_ptr(), C.byref(rings), _stream_handle(stream)))
 
     def log_tensor(self, stream=None):
         import torch

@@ -228,5 +228,14 @@ class VecRoutingEnv:
         }
         return out
 
+    def ingest_transitions(self, buffers) -> None:
+        """transitions() and ``buffers.add()`` in one device pass (PrismaEngine.ingest_transitions,
+        prisma_ingest_transitions): the transitions completed since the previous call go from the
+        decision log straight into a non-prioritized trainer.ReplayBuffers, bit-identical to
+        ``buffers.add(self.transitions())``, and the progress mark advances exactly as transitions()
+        would move it.  No host read.  The uid / hop / t_ns / episode fields of transitions(), which
+        only "NN" / "target" signalling reads, are not produced: those keep the torch path."""
+        self.engine.ingest_transitions(self._consumed, buffers)
+
     def close(self):
         self.engine.close()

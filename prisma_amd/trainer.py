@@ -551,6 +551,25 @@ class QRoutingTrainer:
             keep[:extra] = False
             self._take_pending(keep)
 
+    def _check_fused_ingest(self):
+        if self.prioritized:
+            raise ValueError("observe_env / fused_ingest fill a non-prioritized buffer (the priorities are kept by "
+                             "ReplayBuffers.add): use observe(env.transitions())")
+        if self.signaling != "ideal":
+            raise ValueError("observe_env / fused_ingest need signaling_type='ideal' (hop transitions of 'NN' / "
+                             "'target' wait for signalling packets): use observe(env.transitions())")
+
+    def observe_env(self, env):
+        """observe(env.transitions()) in one device pass (VecRoutingEnv.ingest_transitions,
+        prisma_ingest_transitions): the env's completed transitions go from its decision log straight
+        into the buffers, bit-identical to the torch path, and the nodes' transition counts move by
+        the buffers' ``total``.  No host read.  "ideal" signalling and the non-prioritized buffer
+        only: anything else raises ValueError before the env is touched and keeps the torch path."""
+        self._check_fused_ingest()
+        before = self.buffers.total.clone()
+        env.ingest_transitions(self.buffers)
+        self.transitions_seen += self.buffers.total - before
+
     def _queue_order(self, idx: torch.Tensor) -> torch.Tensor:
         """idx (pending positions) in queue order: by time, ties in arrival order (the upcoming
         list is kept sorted by "time" with a stable sort, forwarder.py:441-442)."""
@@ -871,7 +890,8 @@ def train(env, trainer: QRoutingTrainer, steps: int, train_every: int = 1, sync_
     return losses
 
 
-def train_fused(env, trainer: QRoutingTrainer, launches: int, hops_per_launch: int, train_every: int = 1):
+def train_fused(env, trainer: QRoutingTrainer, launches: int, hops_per_launch: int, train_every: int = 1,
+                fused_ingest: bool = False):
     """Train from in-kernel rollouts: every launch is a fused epsilon-greedy run of up to
     ``hops_per_launch`` hops per replica (VecRoutingEnv.run(..., explore=...), the exploring step
     kernels) instead of one decision per replica per launch as in train().  Per launch: the fused
@@ -885,6 +905,11 @@ def train_fused(env, trainer: QRoutingTrainer, launches: int, hops_per_launch: i
     With QRoutingTrainer(smart_exploration=True) every launch explores by the trainer's action
     history and counts into it (run(..., action_history=trainer.action_history)).
 
+    ``fused_ingest=True`` moves the launch's transitions into the buffers with
+    trainer.observe_env(env) -- one device pass from the decision log into the rings
+    (prisma_ingest_transitions), bit-identical to the default observe(env.transitions()) and
+    without its host reads; non-prioritized buffers only (ValueError before the env is used).
+
     "ideal" signalling only (a transition enters the buffer when it completes; the others wait for
     signalling packets the fused rollout does not hand out).  A launch that writes more records
     than the env's log ring holds would lose transitions silently: RuntimeError; size
@@ -894,6 +919,8 @@ def train_fused(env, trainer: QRoutingTrainer, launches: int, hops_per_launch: i
     if trainer.signaling != "ideal":
         raise ValueError("train_fused needs signaling_type='ideal' (hop transitions of 'NN' / 'target' wait for "
                          "signalling packets): use train()")
+    if fused_ingest:
+        trainer._check_fused_ingest()
     if launches and int(hops_per_launch) < 1:
         raise ValueError("hops_per_launch must be >= 1")
     obs, info = env.reset()
@@ -923,7 +950,10 @@ def train_fused(env, trainer: QRoutingTrainer, launches: int, hops_per_launch: i
                                f"log no longer holds all of the launch's transitions: raise log_capacity or lower "
                                f"hops_per_launch = {hops_per_launch}")
         trainer.advance_clock(cf["now_ns"], cf["episode"])
-        trainer.observe(env.transitions())
+        if fused_ingest:
+            trainer.observe_env(env)
+        else:
+            trainer.observe(env.transitions())
         trainer.check_sync()
         if k % train_every == 0:
             per = trainer.train_step()

@@ -10,8 +10,12 @@
   c  PrismaEngine.run(..., explore=0.1) alone against run() alone, hops/s (the cost of the draw)
   d  PrismaEngine.run(..., explore=0.1, action_history=...) alone against run(..., explore=0.1)
      alone, hops/s (the cost of the action counts and the history-weighted pick)
+  e  what follows a fused launch: buffers.add(env.transitions()) (the torch chain) against
+     env.ingest_transitions(buffers) (prisma_ingest_transitions) on the same log, wall time and peak
+     allocated memory of each, and train_fused() with fused_ingest off and on, transitions/s; run it
+     with --hops 256 and --hops 8192
 
-    python scripts/rollout_bench.py --part a        # or b, c, d; --repeat 2 prints each line twice
+    python scripts/rollout_bench.py --part a        # or b, c, d, e; --repeat 2 prints each line twice
 
 Every part warms up first and is timed between device synchronisations.  bench.py stays the
 headline's yardstick; this script only compares the rollout paths with each other."""
@@ -145,21 +149,84 @@ def part_d(args):
     env.close()
 
 
+def part_e(args):
+    from prisma_amd.trainer import ReplayBuffers
+    env, tr = make(args, pow2_at_least(2 * args.hops))
+    twin = ReplayBuffers(tr.buffers.N, tr.buffers.size, tr.buffers.W, tr.buffers.device)
+    table = tr.q.argmin_table()
+    eps = torch.full((env.topo.n_nodes,), args.eps, dtype=torch.float64, device=env.device)
+    fields = ("obs", "next_obs", "action", "reward", "done", "replica", "next_idx", "count", "total")
+
+    def launch():
+        env.run(table, args.hops, explore=eps)
+        torch.cuda.synchronize()
+        return env._consumed.clone()
+
+    def peak(fn):
+        torch.cuda.synchronize()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        dt, _ = wall(fn)
+        return dt, torch.cuda.max_memory_allocated() - base
+
+    env.reset()
+    for _ in range(args.warmup_launches):                     # both paths once, on the same log
+        c0 = launch()
+        tr.buffers.add(env.transitions())
+        env._consumed = c0
+        env.ingest_transitions(twin)
+    train_fused(env, tr, args.warmup_launches, args.hops, fused_ingest=True)
+    for _ in range(args.repeat):
+        env.reset()
+        for _ in range(args.warmup_launches):
+            launch()
+            env.ingest_transitions(twin)
+        c0 = launch()
+        for f in fields:                                      # the twin starts where the torch path's buffers do
+            getattr(twin, f).copy_(getattr(tr.buffers, f))
+        before = int(tr.buffers.total.sum())
+        t_torch, m_torch = peak(lambda: tr.buffers.add(env.transitions()))
+        n = int(tr.buffers.total.sum()) - before
+        c1 = env._consumed
+        env._consumed = c0
+        t_kernel, m_kernel = peak(lambda: env.ingest_transitions(twin))
+        assert torch.equal(env._consumed, c1) and all(torch.equal(getattr(twin, f), getattr(tr.buffers, f))
+                                                      for f in fields)
+        res = {}
+        for name, fused in (("torch", False), ("kernel", True)):
+            seen0 = int(tr.buffers.total.sum())
+            dt, losses = wall(lambda: train_fused(env, tr, args.launches, args.hops, fused_ingest=fused))
+            res[name] = ((int(tr.buffers.total.sum()) - seen0) / dt, dt, len(losses))
+        out = common(args, "e")
+        out.update(path="after a fused launch: torch chain vs prisma_ingest_transitions", hops_per_launch=args.hops,
+                   log_capacity=env.engine.log_capacity, transitions=n,
+                   torch_add_transitions_s=round(t_torch, 6), ingest_s=round(t_kernel, 6),
+                   torch_over_ingest=round(t_torch / t_kernel, 2),
+                   torch_peak_bytes=int(m_torch), ingest_peak_bytes=int(m_kernel),
+                   launches=args.launches,
+                   train_fused_torch_transitions_per_s=round(res["torch"][0], 1),
+                   train_fused_ingest_transitions_per_s=round(res["kernel"][0], 1),
+                   train_fused_torch_wall_s=round(res["torch"][1], 4),
+                   train_fused_ingest_wall_s=round(res["kernel"][1], 4), train_steps=res["kernel"][2])
+        print(json.dumps(out), flush=True)
+    env.close()
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument("--part", choices=["a", "b", "c", "d"], required=True)
+    p.add_argument("--part", choices=["a", "b", "c", "d", "e"], required=True)
     p.add_argument("--topology", default="abilene")
     p.add_argument("--replicas", type=int, default=4096)
     p.add_argument("--eps", type=float, default=0.1)
     p.add_argument("--batch", type=int, default=512)
-    p.add_argument("--hops", type=int, default=32768, help="hops per replica per fused launch (parts b, c)")
+    p.add_argument("--hops", type=int, default=32768, help="hops per replica per fused launch (parts b, c, d, e)")
     p.add_argument("--launches", type=int, default=3, help="timed fused launches (parts b, c)")
     p.add_argument("--warmup-launches", type=int, default=1)
     p.add_argument("--steps", type=int, default=200, help="timed env steps (part a)")
     p.add_argument("--warmup-steps", type=int, default=20)
     p.add_argument("--repeat", type=int, default=2, help="timed repeats, one JSON line each (the spread)")
     args = p.parse_args(argv)
-    {"a": part_a, "b": part_b, "c": part_c, "d": part_d}[args.part](args)
+    {"a": part_a, "b": part_b, "c": part_c, "d": part_d, "e": part_e}[args.part](args)
 
 
 if __name__ == "__main__":
