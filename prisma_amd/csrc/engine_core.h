@@ -19,6 +19,7 @@
 #include "engine_layout.h"
 #include "numerics.h"
 #include "mrg32k3a.h"
+#include "prio_ladder.h"
 
 using namespace prisma;
 
@@ -353,8 +354,9 @@ struct Sim {
     const CAS BigSig* m_bs;
     uint32_t* lrec;                         // link records [L][kLRec] (HBM)
     // issue priority by launch progress (prio_update): hops of the whole launch (0: off), hops done
-    // before this event loop, and the loop's hop count at which the priority next drops
-    uint32_t prio_total, prio_base, prio_next;
+    // before this event loop, the loop's hop count at which the priority next changes, and the
+    // launch's chunk shift (prio_ladder_shift(prio_total), set with prio_total)
+    uint32_t prio_total, prio_base, prio_next, prio_shift;
 #if PRISMA_TIMING
     mutable uint64_t tsub[2], tlast;             // sub-phase cycles inside apply_decision
     mutable uint64_t tmlp[4];                    // mlp_action phases (timing build)
@@ -400,7 +402,7 @@ __device__ inline void sim_bind(Sim& S, const LV& L, unsigned char* lds, const u
     S.ctrl = true;
     S.mlp_inst = false;
     S.lrec = nullptr;
-    S.prio_total = 0; S.prio_base = 0; S.prio_next = 0xffffffffu;
+    S.prio_total = 0; S.prio_base = 0; S.prio_next = kPrioNever; S.prio_shift = 31u;
 }
 
 // Issue priority by launch progress.  A SIMD arbitrates its waves' issue by priority, then age
@@ -408,21 +410,43 @@ __device__ inline void sim_bind(Sim& S, const LV& L, unsigned char* lds, const u
 // replicas runs ahead and the youngest finishes alone: measured on the headline
 // (scripts/wave_times.py), the 4 waves of a SIMD ended at about 89, 113, 124 and 146 ms of a
 // 146-ms launch, the last ~22 ms with one wave left to hide its own latency.  Here a wave's priority
-// drops as its share of the launch's hops is done (3 below 5/8, 2 below 13/16, 1 below 15/16, then 0),
-// so a wave that is ahead yields issue to the ones behind it and the SIMD keeps all four to the end.
+// follows the share of the launch's hops it has done, so a wave that is ahead yields issue to the
+// ones behind it and the SIMD keeps all four to the end.  The level and the next boundary come
+// from prio_ladder.h (plain C++, tested on the CPU): the fixed thresholds 5/8, 13/16, 15/16
+// (3, 2, 1, then 0) and / or chunks of T / PRISMA_PRIO_CHUNKS hops whose level steps down and wraps,
+// which keep correcting to the launch's end.  Build switches, for A/B variants
+// (scripts/build_variant.sh <name> -DPRISMA_PRIO_CHUNKS=128 -DPRISMA_PRIO_HYBRID_FROM=0):
+//   PRISMA_PRIO_HYBRID_FROM  how many of the fixed thresholds hold before the chunks take over
+//                            (0: chunks from the first hop, the cyclic ladder; 4: thresholds only)
+//   PRISMA_PRIO_CHUNKS       chunk count of the launch (power of two)
+// The shipped defaults are the winners of profiles/prio_ladder/ab_sweep.txt.
 // (round-6 A/B on one box, profiles/r06_ab/ab_prio.txt: thresholds 5/8, 13/16, 15/16 +13.4 % at
 // the headline and +8.9 % at config 3; 1/2, 3/4, 7/8 +13.2 %; 1/4, 1/2, 3/4 +10 %;
 // 7/8, 15/16, 31/32 +4.5 %; a least-progress-first rank over the SIMD's four waves, exchanged
 // through global memory every 64 or 256 hops, -2 %)
+// hops_loop: the hops of this event loop; S.prio_base those of the launch before it (the second
+// loop after spare_restart), so the level is that of the launch's progress wherever the loop
+// stands -- also when finish_pending stepped over a boundary -- and S.prio_next is loop-local.
 __device__ __forceinline__ void prio_update(Sim& S, uint32_t hops_loop) {
-    const uint32_t T = S.prio_total, p = S.prio_base + hops_loop;
-    const uint32_t t1 = T / 2 + T / 8, t2 = T - T / 8 - T / 16, t3 = T - T / 16;
-    uint32_t next;
-    if (p < t1) { __builtin_amdgcn_s_setprio(3); next = t1; }
-    else if (p < t2) { __builtin_amdgcn_s_setprio(2); next = t2; }
-    else if (p < t3) { __builtin_amdgcn_s_setprio(1); next = t3; }
-    else { __builtin_amdgcn_s_setprio(0); next = 0xffffffffu; }
-    S.prio_next = next == 0xffffffffu ? next : next - S.prio_base;
+    // the instances without the ladder (prio_total a constant 0): nothing, so the event loop's test
+    // folds away with it -- the opaque T below would otherwise keep the ladder's code in them
+    if (__builtin_constant_p(S.prio_total) && S.prio_total == 0u) return;
+    // (the launch's progress is the same in every lane, but prio_base -- the restart loop's hops
+    // done -- lives in a VGPR: the whole sum goes through readfirstlane, so in both event-loop
+    // copies the ladder is scalar arithmetic and scalar branches.  As lane values the switch became
+    // exec-masked regions, and s_setprio, which ignores exec, ran in every one of them.)
+    // T opaque here: the thresholds are then derived in this rarely-run block instead of being
+    // hoisted out of the event loop, where each would hold (and spill) an SGPR for the whole launch
+    uint32_t T = S.prio_total;
+    asm volatile("" : "+s"(T));
+    const PrioStep st = prio_ladder(T, S.prio_shift, rfl(S.prio_base + hops_loop));
+    switch (st.level) {                              // (s_setprio takes an immediate)
+    case 3u: __builtin_amdgcn_s_setprio(3); break;
+    case 2u: __builtin_amdgcn_s_setprio(2); break;
+    case 1u: __builtin_amdgcn_s_setprio(1); break;
+    default: __builtin_amdgcn_s_setprio(0); break;
+    }
+    S.prio_next = prio_ladder_local(st.next, S.prio_base);
 }
 
 // Topology reads.  The register-resident engine reads the fixed-offset TopoImage,
@@ -2939,7 +2963,8 @@ __device__ __forceinline__ uint32_t event_loop(const KParams& P, Sim& S, RS& R, 
                                    D.r0, D.deg);
                     H.hops_launch++;
                     if (H.hops_launch >= max_hops) H.stop = 1;
-                    if (H.hops_launch == S.prio_next) prio_update(S, H.hops_launch);
+                    // (>=, not ==: finish_pending's hop before the loop can step over a boundary)
+                    if (H.hops_launch >= S.prio_next) prio_update(S, H.hops_launch);
                     TM_MARK(2);
                 } else {
                     if (lane == 0) {

@@ -48,7 +48,7 @@ __device__ unsigned long long g_wave_times[4 * 65536];
 // reason given above, and rather than one more template parameter, so the existing instances keep
 // their symbol names.
 //
-// S.prio_total: 4-wave instances only (at 2 waves per SIMD, config 4's, the same thresholds lost
+// S.prio_total and S.prio_shift (the ladder): 4-wave instances only (at 2 waves per SIMD, config 4's, thresholds lost
 // 2 %).
 //
 // An episode that ends with hop budget left (fused run with auto_reset) continues into the next
@@ -79,6 +79,7 @@ __device__ unsigned long long g_wave_times[4 * 65536];
     if (TUN) S.ring = (uint32_t*)(P.state + (size_t)r * LC.state_bytes + LC.s_ring);   /* HBM FIFOs */  \
     uint32_t budget = (uint32_t)P.max_hops;                                                             \
     S.prio_total = StepOcc<FS, LS>::waves >= 4 ? budget : 0u;                                           \
+    S.prio_shift = StepOcc<FS, LS>::waves >= 4 ? prio_ladder_shift(budget) : 31u;                       \
     const uint32_t done = event_loop<MLP, StepOcc<FS, LS>::mlp_batch, EXPL_, LQ>(P, S, R, r, budget);   \
     if (P.spare && done < budget) {                                                                     \
         const KParams* kp = (const KParams*)__builtin_amdgcn_kernarg_segment_ptr();                     \

@@ -3,8 +3,11 @@ translation unit: s_memrealtime at each wave's start and end, and its HW_ID / XC
 
   ONLY=prisma_engine_lite.hip bash scripts/build_variant.sh wt -DPRISMA_WAVE_TIMES=1   # here
   python scripts/wave_times.py                                                        # GPU box
-Prints the spread of wave end times over the last launch and how much of the kernel's SIMD time
-the waves were resident."""
+Prints, per launch, the spread of wave end times, how much of the kernel's SIMD time the waves
+were resident, and over the SIMDs that held four waves: their four wave ends (sorted, as offsets
+before the SIMD's last end) and the time they spent with 3, 2 and 1 waves left -- the three phases
+in which a SIMD runs short-handed.  --lib NAME reads prisma_amd/_ablate/libprisma_amd_NAME.so
+(default wt), so a build of another tree (SRC_DIR=... build_variant.sh wt_parent ...) runs beside it."""
 import ctypes as C
 import os
 import sys
@@ -12,7 +15,8 @@ import sys
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-os.environ["PRISMA_LIB"] = os.path.join(ROOT, "prisma_amd", "_ablate", "libprisma_amd_wt.so")
+LIB = sys.argv[sys.argv.index("--lib") + 1] if "--lib" in sys.argv else "wt"
+os.environ["PRISMA_LIB"] = os.path.join(ROOT, "prisma_amd", "_ablate", f"libprisma_amd_{LIB}.so")
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 from prisma_amd.config import engine_params  # noqa: E402
@@ -55,11 +59,20 @@ for it in range(6):
           f"end min/p10/p50/p90/max {np.percentile(e, [0, 10, 50, 90, 100]).round(0).tolist()} us; "
           f"mean life / span {life.mean() / span:.3f}; SIMDs {n_simd}, waves per SIMD {np.bincount(per).nonzero()[0].tolist()}",
           flush=True)
-# per-SIMD: the last wave's end against the SIMD's mean wave end (how long a SIMD runs short-handed)
-order = np.argsort(key)
-ks, ee = key[order], e[order]
-bounds = np.flatnonzero(np.diff(ks)) + 1
-groups = np.split(ee, bounds)
-tail = np.array([g.max() - np.sort(g)[-2] if len(g) > 1 else 0.0 for g in groups])
+    # the SIMDs with four waves: ends sorted per SIMD; phase k = time with k waves left
+    order = np.argsort(key, kind="stable")
+    ks, ee = key[order], e[order]
+    groups = [np.sort(g) for g in np.split(ee, np.flatnonzero(np.diff(ks)) + 1)]
+    four = np.array([g for g in groups if len(g) == 4])
+    if len(four):
+        off = four[:, 3:4] - four                                  # [n, 4]: us before the SIMD's last end
+        ph = np.diff(four, axis=1)                                 # [n, 3]: time with 3, 2, 1 waves
+        q = lambda x: "/".join(f"{v:.0f}" for v in (x.mean(), *np.percentile(x, [10, 50, 90])))
+        print(f"  per SIMD ({len(four)} with 4 waves), mean/p10/p50/p90 us: wave ends before the SIMD's last "
+              f"1st {q(off[:, 0])}, 2nd {q(off[:, 1])}, 3rd {q(off[:, 2])}; time with 3 waves {q(ph[:, 0])}, "
+              f"2 waves {q(ph[:, 1])}, 1 wave {q(ph[:, 2])}; short-handed wave-time "
+              f"{(ph * np.array([1, 2, 3])).sum(axis=1).mean() / (4 * span):.4f} of 4 x span", flush=True)
+# per-SIMD, last launch (groups: its wave ends, sorted): how long the last wave ran alone
+tail = np.array([g[-1] - g[-2] if len(g) > 1 else 0.0 for g in groups])
 print(f"per SIMD, last wave end - second-last: mean {tail.mean():.0f} us, p90 {np.percentile(tail, 90):.0f} us; "
       f"SIMD end spread (max over SIMDs of last end) - (min) {max(g.max() for g in groups) - min(g.max() for g in groups):.0f} us")
