@@ -2847,17 +2847,21 @@ __device__ __forceinline__ bool spare_restart(const KParams&, Sim&, RS&, int, ui
 // MB: mlp_action_reg's batch (the memory-resident engine passes 0)
 // LQ: the MLP is one of the reduced DQN-buffer models (lightq_action_reg with P.lq_dims;
 // register-resident instances of their own)
-template <bool MLP, int MB, int EXPL = 0, bool LQ = false, class RS>
+// FUSED: the launch is a fused table run (P.mode == 2) of an env whose table sits in LDS, known
+// at compile time (step_kernel.h prisma_step_kernel_fused_t): the external-policy exit of an
+// arrival, the PENDING record, the P.actions branch and the table's HBM pointer are compiled out
+template <bool MLP, int MB, int EXPL = 0, bool LQ = false, bool FUSED = false, class RS>
 __device__ __forceinline__ uint32_t event_loop(const KParams& P, Sim& S, RS& R, int r, uint32_t max_hops) {
     const int lane = S.lane;
     const LV& L = S.lv;
     const bool mlp_mode = MLP;
     S.mlp_inst = MLP;
-    const bool table_mode = (P.mode == 2) || mlp_mode;            // fused in-kernel policy
+    static_assert(!FUSED || (!MLP && !RS::kMem), "the fused-only instances are register-engine table instances");
+    const bool table_mode = FUSED || (P.mode == 2) || mlp_mode;   // fused in-kernel policy
     S.mlp = P.mlp;
     S.mlp_rp = P.mlp_rp;
-    S.table_g = P.table;
-    S.tab_lds = S.tab_lds && ((CLayout*)P.lay)->table_in_lds != 0u;
+    S.table_g = FUSED ? nullptr : P.table;
+    S.tab_lds = FUSED || (S.tab_lds && ((CLayout*)P.lay)->table_in_lds != 0u);
     const uint32_t NN = (uint32_t)L.N();
     Hot H;
     hot_load(S, H);

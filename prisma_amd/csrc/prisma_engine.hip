@@ -115,6 +115,7 @@ __global__ void __launch_bounds__(64) prisma_reset_kernel_t(KParams P) {
 // prisma_engine_smart_mlp.hip / prisma_engine_smart_lightq.hip
 const void* prisma_pick_step_lite(int fs, int ls, bool tun);
 const void* prisma_pick_step_lite_mlp(int fs, int ls, bool tun);
+const void* prisma_pick_step_fused(int fs, int ls, bool tun);
 const void* prisma_pick_step_ctrl_mlp(int fs, int ls, bool tun);
 const void* prisma_pick_step_explore(int fs, int ls, bool tun);
 const void* prisma_pick_step_explore_mlp(int fs, int ls, bool tun);
@@ -331,6 +332,7 @@ struct prisma_env {
     Layout* d_lay = nullptr;
     const void* k_step = nullptr;
     const void* k_step_mlp = nullptr;
+    const void* k_fused = nullptr;       // fused-only table instance (run_fused), or null: k_step runs tables too
     const void* k_reset = nullptr;
     const void* k_explore = nullptr;     // exploring instances (prisma_run_explore): register engine
     const void* k_explore_mlp = nullptr; // without the ctrl paths only
@@ -1143,6 +1145,10 @@ extern "C" int prisma_create(const prisma_topology_t* topo, const prisma_params_
         e->k_step = pick(L.FS, L.LS, L.tunnels != 0u);
         e->k_reset = pick_reset(L.FS, L.LS);
         e->k_step_mlp = pick_mlp(L.FS, L.LS, L.tunnels != 0u);
+        // fused table runs have instances of their own (step_kernel.h FUSED) where the env is an
+        // identity overlay without the ctrl paths and its table sits in LDS (the picker has none
+        // for tunnelled overlays); elsewhere k_step serves them as well
+        if (!ctrl && L.table_in_lds) e->k_fused = prisma_pick_step_fused(L.FS, L.LS, L.tunnels != 0u);
         if (!ctrl) {
             e->k_explore = prisma_pick_step_explore(L.FS, L.LS, L.tunnels != 0u);
             e->k_explore_mlp = prisma_pick_step_explore_mlp(L.FS, L.LS, L.tunnels != 0u);
@@ -1164,6 +1170,7 @@ extern "C" int prisma_create(const prisma_topology_t* topo, const prisma_params_
     (void)hipFuncSetAttribute(e->k_step_mlp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_mlp_bytes);
     (void)hipFuncSetAttribute(e->k_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bytes);
     (void)hipFuncSetAttribute(e->k_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bytes);
+    if (e->k_fused) (void)hipFuncSetAttribute(e->k_fused, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bytes);
     if (e->k_explore) (void)hipFuncSetAttribute(e->k_explore, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bytes);
     if (e->k_explore_mlp)
         (void)hipFuncSetAttribute(e->k_explore_mlp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_mlp_bytes);
@@ -1304,7 +1311,7 @@ static int run_fused(prisma_env_t* e, int32_t policy, const void* policy_data, i
     const void* kern = action_hist ? (lightq ? e->k_smart_lightq : P.mode == 4 ? e->k_smart_mlp : e->k_smart)
                      : lightq ? (explore_thr ? e->k_explore_lightq : e->k_lightq)
                      : explore_thr ? (P.mode == 4 ? e->k_explore_mlp : e->k_explore)
-                                   : (P.mode == 4 ? e->k_step_mlp : e->k_step);
+                                   : (P.mode == 4 ? e->k_step_mlp : e->k_fused ? e->k_fused : e->k_step);
     int rc = launch(e, kern, P, stream);
     // with auto_reset (register engine) the step kernel already continued every replica whose
     // episode ended into the next one; this launch refreshes the spare images it used, and

@@ -1,7 +1,8 @@
 // step_kernel.h -- the register-resident engine's step kernel template and its instance table,
 // included by prisma_engine.hip (instances with the --train echo / notify_dest code, CTRL) and
 // prisma_engine_lite.hip (instances without it: the compiler allocates registers for every
-// path a kernel contains, and these rarely-taken ones cost the common case ~2 %).
+// path a kernel contains, and these rarely-taken ones cost the common case ~2 %), and by
+// prisma_engine_fused.hip (table instances for fused runs only, without the external-policy path).
 #pragma once
 #include "engine_core.h"
 
@@ -23,7 +24,16 @@ template <int FS, int LS> struct StepOcc {
 // a shared inlined function taking the arguments by reference the headline instance came out
 // with 7 more SGPR spill slots and the DQN-buffer one with 16 B more scratch.)  LQ: the MLP is the
 // reduced DQN-buffer models' decision (engine_core.h lightq_action_reg; widths in KParams::lq_dims)
-// -- instance sets of their own again, greedy and exploring, without the ctrl paths.
+// -- instance sets of their own again, greedy and exploring, without the ctrl paths.  FUSED: the
+// table instances that only fused runs (prisma_run with a table) launch, for identity-overlay envs
+// without the ctrl paths whose table sits in LDS: event_loop's table_mode and the table's place are compile-time
+// constants there, so the external-policy exit of an arrival (the Decision stored to the header,
+// the pending observation, the PENDING record), the P.actions branch and the HBM table pointer are
+// not in the kernel.  The MLP / LQ instances fold table_mode already (MLP is a template argument);
+// the general table instances keep the run-time value and serve prisma_step, the ctrl envs, envs
+// whose table stays in HBM and the tunnelled overlays (A/B, profiles/fused_inst/: headline +3.2 %,
+// SP at its shape +2.6 %, but config 3's SP line on the tunnelled (2, 1) instance -0.35 % at a
+// 0.25 % spread, so those are not instantiated).
 #if PRISMA_WAVE_TIMES
 // diagnostic build only (scripts/wave_times.py): each replica's wave start / end (s_memrealtime,
 // 100 MHz) and hardware ids of its last launch
@@ -43,10 +53,10 @@ __device__ unsigned long long g_wave_times[4 * 65536];
 #define WT_END() do { } while (0)
 #endif
 
-// The kernel body, shared by the two kernel templates below (EXPL_: 0 greedy, 1 uniform
-// exploration, 2 history-weighted exploration).  A macro rather than an inlined function, for the
-// reason given above, and rather than one more template parameter, so the existing instances keep
-// their symbol names.
+// The kernel body, shared by the kernel templates below (EXPL_: 0 greedy, 1 uniform
+// exploration, 2 history-weighted exploration; FUSED_: the fused-only table instances).  A macro
+// rather than an inlined function, for the reason given above, and rather than one more template
+// parameter, so the existing instances keep their symbol names.
 //
 // S.prio_total and S.prio_shift (the ladder): 4-wave instances only (at 2 waves per SIMD, config 4's, thresholds lost
 // 2 %).
@@ -62,7 +72,7 @@ __device__ unsigned long long g_wave_times[4 * 65536];
 // scratch).  The reloaded arguments sit in VGPRs; the smart instances move the history pointer
 // to SGPRs there (two more VGPRs held across the second loop made the headline shape's instance
 // spill 4 VGPRs in that loop's prologue: 20 B scratch, none with the pointer in SGPRs).
-#define PRISMA_STEP_KERNEL_BODY(EXPL_)                                                                  \
+#define PRISMA_STEP_KERNEL_BODY(EXPL_, FUSED_)                                                          \
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];                                 \
     const int r = blockIdx.x, lane = threadIdx.x;                                                       \
     WT_START();                                                                                         \
@@ -80,7 +90,7 @@ __device__ unsigned long long g_wave_times[4 * 65536];
     uint32_t budget = (uint32_t)P.max_hops;                                                             \
     S.prio_total = StepOcc<FS, LS>::waves >= 4 ? budget : 0u;                                           \
     S.prio_shift = StepOcc<FS, LS>::waves >= 4 ? prio_ladder_shift(budget) : 31u;                       \
-    const uint32_t done = event_loop<MLP, StepOcc<FS, LS>::mlp_batch, EXPL_, LQ>(P, S, R, r, budget);   \
+    const uint32_t done = event_loop<MLP, StepOcc<FS, LS>::mlp_batch, EXPL_, LQ, FUSED_>(P, S, R, r, budget); \
     if (P.spare && done < budget) {                                                                     \
         const KParams* kp = (const KParams*)__builtin_amdgcn_kernarg_segment_ptr();                     \
         asm volatile("" : "+s"(kp));                                                                    \
@@ -88,7 +98,7 @@ __device__ unsigned long long g_wave_times[4 * 65536];
         if (EXPL_ == 2) P2.action_hist = rfl_ptr(P2.action_hist);                                       \
         if (spare_restart(P2, S, R, r, done, budget)) {                                                 \
             S.prio_base = done;                                                                         \
-            event_loop<MLP, StepOcc<FS, LS>::mlp_batch, EXPL_, LQ>(P2, S, R, r, budget);                \
+            event_loop<MLP, StepOcc<FS, LS>::mlp_batch, EXPL_, LQ, FUSED_>(P2, S, R, r, budget);        \
             stage_out(lds, P2, r, lane, R);                                                             \
             WT_END();                                                                                   \
             return;                                                                                     \
@@ -100,7 +110,7 @@ __device__ unsigned long long g_wave_times[4 * 65536];
 template <int FS, int LS, bool MLP, bool TUN, bool CTRL, bool EXPL = false, bool LQ = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(StepOcc<FS, LS>::waves)))
 prisma_step_kernel_t(KParams P) {
-    PRISMA_STEP_KERNEL_BODY(EXPL ? 1 : 0)
+    PRISMA_STEP_KERNEL_BODY(EXPL ? 1 : 0, false)
 }
 
 // SMART: the instances with history-weighted exploration (engine_core.h smart_explore_action;
@@ -110,7 +120,17 @@ template <int FS, int LS, bool MLP, bool TUN, bool LQ>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(StepOcc<FS, LS>::waves)))
 prisma_step_kernel_smart_t(KParams P) {
     constexpr bool CTRL = false;
-    PRISMA_STEP_KERNEL_BODY(2)
+    PRISMA_STEP_KERNEL_BODY(2, false)
+}
+
+// FUSED: the table instances of fused runs (above).  The parameters end in TUN, CTRL as the
+// general template's label does; only TUN = false, CTRL = false is instantiated.
+template <int FS, int LS, bool TUN, bool CTRL>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(StepOcc<FS, LS>::waves)))
+prisma_step_kernel_fused_t(KParams P) {
+    static_assert(!CTRL, "the fused-only instances carry no ctrl paths");
+    constexpr bool MLP = false, LQ = false;
+    PRISMA_STEP_KERNEL_BODY(0, true)
 }
 
 // instantiations: flow slots FS in {1,2,4,8} (F <= 512), link slots LS in {1,2,4} (L <= 256)
@@ -127,15 +147,40 @@ template <int FS, int LS, bool CTRL, bool MLP, bool EXPL = false, bool LQ = fals
 // and prisma_engine_lite_mlp.hip (without the ctrl paths), prisma_engine_explore.hip and
 // prisma_engine_explore_mlp.hip (EXPL, without the ctrl paths), prisma_engine_lightq.hip and
 // prisma_engine_explore_lightq.hip (LQ, without the ctrl paths), prisma_engine_smart.hip,
-// prisma_engine_smart_mlp.hip and prisma_engine_smart_lightq.hip (SMART, without the ctrl paths)
+// prisma_engine_smart_mlp.hip and prisma_engine_smart_lightq.hip (SMART, without the ctrl paths),
+// prisma_engine_fused.hip (FUSED tables, without the ctrl paths)
 template <bool CTRL, bool MLP, bool EXPL = false, bool LQ = false>
 static const void* pick_step(int fs, int ls, bool tun) {
 #ifdef PRISMA_DEV_HEADLINE
-    // register-allocation experiments only: compile the headline instance alone
+    // register-allocation experiments only: compile the headline instance alone -- the fused
+    // one (pick_step_fused), or with -DPRISMA_DEV_GENERAL the general one prisma_step launches
+#ifdef PRISMA_DEV_GENERAL
     return (!CTRL && !MLP && !EXPL && !LQ && fs == 2 && ls == 1 && !tun) ? (const void*)prisma_step_kernel_t<2, 1, false, false, false>
                                                          : nullptr;
 #else
+    return nullptr;
+#endif
+#else
 #define PK(F_, L_) if (fs == F_ && ls == L_) return step_kernel<F_, L_, CTRL, MLP, EXPL, LQ>(tun);
+    PK(1, 1) PK(1, 2) PK(1, 4) PK(2, 1) PK(2, 2) PK(2, 4) PK(4, 1) PK(4, 2) PK(4, 4) PK(8, 1) PK(8, 2) PK(8, 4)
+#undef PK
+    return nullptr;
+#endif
+}
+
+// (a template as pick_step is, so only the translation unit that calls it instantiates the kernels)
+template <bool CTRL>
+static const void* pick_step_fused(int fs, int ls, bool tun) {
+    static_assert(!CTRL, "the fused-only instances carry no ctrl paths");
+#ifdef PRISMA_DEV_HEADLINE
+#ifdef PRISMA_DEV_GENERAL
+    return nullptr;
+#else
+    return (fs == 2 && ls == 1 && !tun) ? (const void*)prisma_step_kernel_fused_t<2, 1, false, CTRL> : nullptr;
+#endif
+#else
+    if (tun) return nullptr;
+#define PK(F_, L_) if (fs == F_ && ls == L_) return (const void*)prisma_step_kernel_fused_t<F_, L_, false, CTRL>;
     PK(1, 1) PK(1, 2) PK(1, 4) PK(2, 1) PK(2, 2) PK(2, 4) PK(4, 1) PK(4, 2) PK(4, 4) PK(8, 1) PK(8, 2) PK(8, 4)
 #undef PK
     return nullptr;

@@ -240,6 +240,29 @@ def plan(topo: Topology, params: dict) -> dict:
     return {k: int(getattr(out, k)) for k, _ in _Plan._fields_}
 
 
+def step_kernel_names(ki: dict, pl: dict) -> dict:
+    """Demangled names of the step-kernel instances an env launches, from prisma_kernel_info's
+    and prisma_plan's answers (the library's own choice, prisma_create and run_fused, restated):
+    `step` by prisma_step, `table` by prisma_run with a table, `mlp` by prisma_run with DQN-buffer
+    weights.  Fused table runs have instances of their own (prisma_step_kernel_fused_t) on the
+    register-resident engine where the env is an identity overlay without the ctrl paths and its
+    table sits in LDS (the plan's LDS per replica then exceeds the state image's part); elsewhere
+    `table` is `step`."""
+    ctrl = "true" if ki["ctrl"] else "false"
+    if ki["engine"] == PRISMA_ENGINE_MEMORY:
+        step = f"prisma_mem_step_kernel<false, {ctrl}>"
+        return {"step": step, "table": step, "mlp": f"prisma_mem_step_kernel<true, {ctrl}>"}
+    fs, ls = ki["flow_slots"], ki["link_slots"]
+    tun = "true" if ki["tunnels"] else "false"
+    # template arguments: slots, in-kernel MLP, tunnels, --train/notify_dest paths (the
+    # greedy instances; the sixth, EXPL, is true for the ones run(..., explore=) launches)
+    step = f"prisma_step_kernel_t<{fs}, {ls}, false, {tun}, {ctrl}>"
+    fused = not ki["ctrl"] and not ki["tunnels"] and pl["lds_bytes"] > pl["lds_state_bytes"]
+    return {"step": step,
+            "table": f"prisma_step_kernel_fused_t<{fs}, {ls}, false, false>" if fused else step,
+            "mlp": f"prisma_step_kernel_t<{fs}, {ls}, true, {tun}, {ctrl}>"}
+
+
 class PrismaEngine:
     """R replicas of one scenario on one MI355X (device memory owned by the library)."""
 
@@ -272,17 +295,13 @@ class PrismaEngine:
         # made, reported by the library; the demangled names are for profiles)
         ki = self.kernel_info()
         self.engine_kind = ki["engine"]
-        ctrl = "true" if ki["ctrl"] else "false"
-        if self.engine_kind == PRISMA_ENGINE_MEMORY:
-            self.kernel_name = f"prisma_mem_step_kernel<false, {ctrl}>"
-            self.kernel_name_mlp = f"prisma_mem_step_kernel<true, {ctrl}>"
-        else:
-            fs, ls = ki["flow_slots"], ki["link_slots"]
-            tun = "true" if ki["tunnels"] else "false"
-            # template arguments: slots, in-kernel MLP, tunnels, --train/notify_dest paths (the
-            # greedy instances; the sixth, EXPL, is true for the ones run(..., explore=) launches)
-            self.kernel_name = f"prisma_step_kernel_t<{fs}, {ls}, false, {tun}, {ctrl}>"
-            self.kernel_name_mlp = f"prisma_step_kernel_t<{fs}, {ls}, true, {tun}, {ctrl}>"
+        # kernel_name: what run() with a table launches (bench.py's roofline.kernel, the
+        # profiles' filter); kernel_name_step: what step() launches; kernel_name_mlp: run() with
+        # DQN-buffer weights
+        names = step_kernel_names(ki, plan(topo, params))
+        self.kernel_name = names["table"]
+        self.kernel_name_step = names["step"]
+        self.kernel_name_mlp = names["mlp"]
         self.obs = torch.zeros((self.R, self.W), dtype=torch.int32, device=self.torch_device)
         self.mask = torch.zeros(self.R, dtype=torch.uint8, device=self.torch_device)
         self.node = torch.zeros(self.R, dtype=torch.int32, device=self.torch_device)

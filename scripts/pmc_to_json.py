@@ -7,7 +7,7 @@ XCD's active cycles = GRBM_GUI_ACTIVE / 8; salu_busy = SALU instructions / (cycl
 (one scalar unit per CU, at most one issue per cycle); valu_busy = 2 x VALU instructions /
 (cycles x 1024 SIMDs) (a wave64 VALU instruction occupies a SIMD-32 for 2 cycles).
 
-HBM bytes per launch of the step kernel (prisma_step_kernel_t / prisma_mem_step_kernel)
+HBM bytes per launch of the step kernel (prisma_step_kernel_t / prisma_step_kernel_fused_t / prisma_mem_step_kernel)
 = 2 * FETCH_SIZE * 1024 + WRITE_SIZE * 1024
 (MI355X_MICROARCH.md 'HBM': FETCH_SIZE counts half the bytes of wide coalesced reads on
 gfx950 — our staging reads are 16 B/lane; WRITE_SIZE is exact for 16-B stores, our

@@ -21,7 +21,7 @@ if sys.argv[1] == "build":
     from prisma_amd import buildid
     # `build mem` / `build lite_mlp`: that translation unit alone with the probes
     only = {"mem": "prisma_engine_mem.hip", "lite_mlp": "prisma_engine_lite_mlp.hip",
-            "lite": "prisma_engine_lite.hip"}.get(sys.argv[2]) if sys.argv[2:] else None
+            "lite": "prisma_engine_lite.hip", "fused": "prisma_engine_fused.hip"}.get(sys.argv[2]) if sys.argv[2:] else None
     objs, procs = [], []
     for f in buildid.ENGINE_SOURCES:
         if only and f != only:
@@ -59,13 +59,15 @@ eng = PrismaEngine(topo, engine_params(topo, sim_time_s=60.0, ping_as_obs=PAO, a
                                       log_capacity=65536 if topo.n_links > 256 else 8192), R)
 lib = load_library()
 # the kernels without the --train / notify_dest paths live in their own translation unit
-# (one translation unit per instance set: step_kernel.h; kernel name <FS, LS, MLP, TUN, CTRL>)
+# (one translation unit per instance set: step_kernel.h; kernel name <FS, LS, MLP, TUN, CTRL>, or
+# prisma_step_kernel_fused_t<FS, LS, TUN, CTRL>: the table instances of fused runs)
 _kname = eng.kernel_name_mlp if POLICY == "dqn_buffer" else eng.kernel_name
 _targs = [a.strip() for a in _kname.split("<")[-1].rstrip(">").split(",")]
-timing = lib.prisma_debug_timing_mem if eng.engine_kind == 2 else getattr(
-    lib, {("false", "true"): "prisma_debug_timing", ("true", "true"): "prisma_debug_timing_mlp",
-          ("false", "false"): "prisma_debug_timing_lite",
-          ("true", "false"): "prisma_debug_timing_lite_mlp"}[(_targs[2], _targs[4])])
+timing = lib.prisma_debug_timing_mem if eng.engine_kind == 2 else (
+    lib.prisma_debug_timing_fused if _kname.startswith("prisma_step_kernel_fused_t<") else getattr(
+        lib, {("false", "true"): "prisma_debug_timing", ("true", "true"): "prisma_debug_timing_mlp",
+              ("false", "false"): "prisma_debug_timing_lite",
+              ("true", "false"): "prisma_debug_timing_lite_mlp"}[(_targs[2], _targs[4])]))
 timing.argtypes = [C.c_void_p]
 if POLICY == "dqn_buffer":
     table = StackedQNet(topo, "buffer", seed=1234, device="cuda").pack()

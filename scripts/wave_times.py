@@ -1,7 +1,7 @@
-"""Diagnostic: how evenly the headline's waves finish (a -DPRISMA_WAVE_TIMES=1 build of the lite
-translation unit: s_memrealtime at each wave's start and end, and its HW_ID / XCC_ID).
+"""Diagnostic: how evenly the headline's waves finish (a -DPRISMA_WAVE_TIMES=1 build of the fused
+table translation unit, whose instance the headline launches: s_memrealtime at each wave's start and end, and its HW_ID / XCC_ID).
 
-  ONLY=prisma_engine_lite.hip bash scripts/build_variant.sh wt -DPRISMA_WAVE_TIMES=1   # here
+  ONLY=prisma_engine_fused.hip bash scripts/build_variant.sh wt -DPRISMA_WAVE_TIMES=1   # here
   python scripts/wave_times.py                                                        # GPU box
 Prints, per launch, the spread of wave end times, how much of the kernel's SIMD time the waves
 were resident, and over the SIMDs that held four waves: their four wave ends (sorted, as offsets
@@ -29,7 +29,8 @@ HOPS = int(sys.argv[sys.argv.index("--hops") + 1]) if "--hops" in sys.argv else 
 topo = Topology.example("abilene")
 eng = PrismaEngine(topo, engine_params(topo, sim_time_s=60.0, ping_as_obs=1, auto_reset=1, log_capacity=8192), R)
 lib = load_library()
-fn = lib.prisma_debug_wave_times_lite
+assert eng.kernel_name.startswith("prisma_step_kernel_fused_t<"), eng.kernel_name
+fn = lib.prisma_debug_wave_times_fused
 fn.argtypes = [C.c_void_p, C.c_int]
 table = StackedQNet(topo, "routing", seed=1234, device="cuda").argmin_table()
 eng.reset(0)
