@@ -446,6 +446,69 @@ int prisma_run_explore_smart(prisma_env_t* env, int32_t policy, const void* poli
                              int32_t max_hops, const uint32_t* explore_thr,
                              uint32_t* action_hist, uint64_t hist_words, void* stream);
 
+/* Fused stochastic multipath routing: the reference's "opt" agent
+ * (forwarder.py:87-88, 192-194; utils.py:161-199 optimal_routing_decision),
+ * whose action depends on the packet's source, on the flow fraction the
+ * packet was assigned at its previous hop (its `tag`) and on a random draw.
+ * The same contract as prisma_run (hop budget, auto_reset, the next-episode
+ * restart), with a routing matrix in place of a policy.
+ *
+ * The tag.  The reference's tag is always routing[src][dst][the edge the
+ * previous decision took] (both branches of optimal_routing_decision return
+ * the fraction of the edge they chose; a new packet carries None), so it
+ * needs no per-packet state: it follows from the previous decision record's
+ * (node, action) and the packet's source.
+ *
+ * The float test made integer.  The reference's `tag in prob_to_neighbors and
+ * tag < 1` compares float64 values.  The host gives every entry of
+ * routing[s][t][:] a class: the distinct values x with 0 < x < 1 in ascending
+ * order get classes 1, 2, ...; the value 0 and values >= 1 get class 0.  Two
+ * entries are equal as float64 and below 1 exactly when their classes are
+ * equal and non-zero.  At most 255 classes per (s, t).
+ *
+ * The table.  tab: device uint32 [NO][NO][T], s and t overlay indices (NO
+ * overlay nodes; the node ids themselves on an identity overlay), T and
+ * row[] those of prisma_action_history_layout (overlay CSR order: node
+ * ascending, neighbour ascending -- list(G.edges) of the reference's
+ * DiGraph).  Bits 24-31 of an entry hold the class, bits 0-23 the weight
+ * wt = min(floor(p / rowsum * 2^24 + 0.5), 2^24 - 1), rowsum the float64 sum
+ * of node v's deg entries for (s, t); 0 where rowsum == 0.
+ *
+ * The decision.  For data decision d (the numbering of the records' `prev`)
+ * of episode e at node v of overlay degree deg, in replica r, for a packet
+ * with source s, destination t and previous decision (u, a_u) or none:
+ *
+ *   c_prev = (prev exists and 0 <= a_u < deg(u)) ? cls(tab[s][t][row[u] + a_u]) : 0
+ *   M      = { i < deg : cls(tab[s][t][row[v] + i]) == c_prev }
+ *   if c_prev != 0 and M not empty:   a = min M                      (no draw)
+ *   else:  c = philox4x32_10(ctr = {d, 0, e, 3}, key = {seed & 0xffffffff, replica_base + r})
+ *          W = sum_i wt_i  (< 2^30 since deg <= 55)
+ *          a = W == 0 ? (uint32)(((uint64)c[1] * deg) >> 32)
+ *                     : min { i : wt_0 + ... + wt_i > u },  u = (uint32)(((uint64)c[1] * W) >> 32)
+ *
+ * Counter word 3 = 3 keeps the draw apart from the flow start offsets (0),
+ * the send delays (1) and exploration (2).  Destination arrivals and control
+ * packets draw nothing.  Defined, not copied: Philox replaces numpy's global
+ * stream; probabilities are quantised to 24 bits (an edge below 2^-25 of its
+ * row is never drawn); an all-zero row (a NaN and a crash in the reference)
+ * takes the uniform pick.
+ *
+ * The source is the source of the arriving relay entry, or the arrival node
+ * for a fresh packet.  On a tunnelled overlay the relay entries carry no
+ * source: there it is the node of the first record of the packet's `prev`
+ * chain, and a packet whose chain no longer lies within the last
+ * log_capacity decisions sets PRISMA_EBIT_LOGWRAP (its decision is recorded
+ * with action -1).
+ *
+ * `tab` is read during the launch and constant over it.  The kernels exist
+ * for the register-resident engine without the ctrl paths: an env whose
+ * prisma_kernel_info reports ctrl = 1 or the memory-resident engine gets
+ * PRISMA_ERR_CONFIG; a NULL tab or tab_words != NO * NO * T is
+ * PRISMA_ERR_ARG.  (Added without an ABI version change: no struct or
+ * signature moved.) */
+int prisma_run_stochastic(prisma_env_t* env, const uint32_t* tab, uint64_t tab_words,
+                          int32_t max_hops, void* stream);
+
 /* Copy per-replica counters (n_replicas entries) to host memory.
  * Synchronises `stream`. */
 int prisma_read_counters(prisma_env_t* env, prisma_counters_t* host_out,

@@ -32,6 +32,10 @@ AGENT_TYPES = ["dqn_buffer", "dqn_routing", "dqn_buffer_fp", "dqn_buffer_lite", 
 AGENT_MODEL_KINDS = {"dqn_buffer": "buffer", "dqn_routing": "routing", "dqn_buffer_lite": "buffer_lite",
                      "dqn_buffer_lighter": "buffer_lighter", "dqn_buffer_lighter_2": "buffer_lighter_2",
                      "dqn_buffer_lighter_3": "buffer_lighter_3"}
+# the agent types without a network whose decision runs in the fused kernels: agent_type -> what
+# VecRoutingEnv.run takes -- "table": a uint8 [N, N] next-hop table (topology.sp_next_hop_table);
+# "opt": model="opt" with the packed routing table of optrouting.pack_routing
+AGENT_FUSED_KINDS = {"sp": "table", "opt": "opt"}
 
 
 def build_parser() -> argparse.ArgumentParser:

@@ -110,6 +110,8 @@ struct KParams {
                                  // weights in `mlp` / `mlp_rp`, else 0; after explore_thr for the same reason
     uint32_t* action_hist;       // [R][T] per-action counts (prisma_run_explore_smart, the smart instances), or
                                  // null; T = ovrow[N].  Last again: no other instance's kernarg offset moves
+    const uint32_t* stoch_tab;   // [NO][NO][T] class << 24 | weight (prisma_run_stochastic, the stoch instances), or
+                                 // null; last once more
 };
 
 // ---------------------------------------------------------------------------
@@ -2126,6 +2128,7 @@ __device__ __forceinline__ void wire_pop(const Sim& S, RS& R, const Hot& H, uint
 struct Decision {
     uint32_t x, dst, start, uid, v, d; double reward; int32_t prev; uint32_t obs, flags, last, ttl;
     int32_t r0, deg;             // register-resident engine: node v's row pointer and degree (r0 < 0: not read)
+    uint32_t pact;               // a relayed packet's previous record's word 7 (its action byte: stoch_action)
 };
 
 // a control packet (or a data packet inside a tunnel) continues along the
@@ -2357,7 +2360,7 @@ __device__ __forceinline__ int on_arrive(const Sim& S, RS& R, Hot& H, uint32_t l
         // packet to the last hop, unless this node is the packet's source (:303-306)
         const uint32_t echo = (S.ctrl && L.train() && v != ent_src(x, v)) ? PEND_ECHO : 0u;
         D.x = x; D.dst = dst; D.start = start; D.uid = uid; D.v = v; D.d = d; D.reward = reward; D.prev = prev;
-        D.obs = o; D.flags = echo; D.last = last; D.ttl = ttl;
+        D.obs = o; D.flags = echo; D.last = last; D.ttl = ttl; D.pact = rfl(pw.y);
         if (dst == v) {                                             // getGameOver
             write_record(S, H, d, reward, uid, prev, v, dst, start, -1, PRISMA_ST_DESTINATION, o, ttl);
             if (!fused && S.ctrl && L.notify_dest()) {              // the agent is notified (done=True)
@@ -2765,6 +2768,91 @@ __device__ __forceinline__ int smart_explore_action(const Sim& S, const Hot& H, 
     return (int)a;
 }
 
+// Stochastic multipath routing (prisma_run_stochastic, the stoch instances; include/prisma.h
+// states the rule): the reference's "opt" agent.  tab[s][t][:] holds, per overlay edge in the
+// action-history order, a class in bits 24-31 and a 24-bit weight in bits 0-23.  A packet follows
+// the first edge of the deciding node whose class equals that of the edge its previous decision
+// took (the reference's per-packet tag, which is always that edge's fraction); otherwise it draws
+// an edge by the weights of the node's row.
+//
+// Every operand is wave-uniform, so all 64 lanes are active throughout.  Lane i < deg loads its
+// entry (one coalesced load; lanes >= deg contribute 0), the previous edge's entry is one uniform
+// load, a ballot of class matches plus find-first is the follow branch, and the draw is one
+// inclusive 32-bit DPP scan of the weights (W in lane 63; deg <= 55 weights below 2^24, so no
+// carry) with a ballot of prefix > u plus find-first: u < W, so a lane below deg matches first.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ uint32_t dpp_scan_step_u32(uint32_t v) {
+    // lanes with no source (row start, masked rows) take 0
+    return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);
+}
+// inclusive prefix sum over the 64 lanes (all active)
+__device__ __forceinline__ uint32_t wave_scan_u32(uint32_t v) {
+    v = dpp_scan_step_u32<0x111, 0xF>(v);   // row_shr:1
+    v = dpp_scan_step_u32<0x112, 0xF>(v);   // row_shr:2
+    v = dpp_scan_step_u32<0x114, 0xF>(v);   // row_shr:4
+    v = dpp_scan_step_u32<0x118, 0xF>(v);   // row_shr:8
+    v = dpp_scan_step_u32<0x142, 0xA>(v);   // row_bcast:15 into rows 1 and 3
+    v = dpp_scan_step_u32<0x143, 0xC>(v);   // row_bcast:31 into rows 2 and 3
+    return v;
+}
+
+// The source of the packet whose previous decision is record p, on the instances whose relay
+// entries carry no source (relay_ip): the node of the first record of the packet's `prev` chain.
+// Every link must point backwards and stay inside the log as seen from decision d; a chain that
+// does not (its head has been overwritten) returns kNoLink.
+__device__ __forceinline__ uint32_t stoch_chain_src(const Sim& S, uint32_t d, uint32_t p) {
+    for (;;) {
+        const uint32_t q = record_word(S, p, 12);
+        if ((int32_t)q < 0) return record_word(S, p, 24) & 255u;
+        if (q >= p || d - q >= S.lv.log_cap()) return kNoLink;
+        p = q;
+    }
+}
+
+// d, v, dst: the decision, its node and the packet's destination; x: the arriving entry; prev: the
+// previous decision's record index, or < 0 for a fresh packet; pu, pa: that record's node and
+// action byte (ignored when prev < 0)
+__device__ __forceinline__ int stoch_action(const Sim& S, Hot& H, const uint32_t* __restrict__ tab, uint32_t d,
+                                            uint32_t v, uint32_t dst, uint32_t x, int32_t prev, uint32_t pu,
+                                            uint32_t pa) {
+    v = rfl(v); dst = rfl(dst); x = rfl(x); pu = rfl(pu); pa = rfl(pa);
+    const bool has_prev = (int32_t)rfl((uint32_t)prev) >= 0;
+    const uint32_t lane = (uint32_t)S.lane;
+    const uint32_t NN = (uint32_t)S.lv.N(), NO = (uint32_t)S.lv.NO();
+    uint32_t src = ent_src(x, v);
+    if (relay_ip(S) && has_prev) {
+        src = stoch_chain_src(S, rfl(d), rfl((uint32_t)prev));
+        if (src == kNoLink) { fail(H, PRISMA_EBIT_LOGWRAP); return -1; }
+    }
+    const uint32_t si = S.tun ? rfl((uint32_t)S.T->ovi[src & 255u]) : src;
+    const uint32_t ti = S.tun ? rfl((uint32_t)S.T->ovi[dst & 255u]) : dst;
+    const uint32_t r0 = rfl((uint32_t)t_ovrow(S, v));
+    const uint32_t deg = rfl((uint32_t)t_ovrow(S, v + 1)) - r0;
+    const bool ok = si < NO && ti < NO;             // (always: flows run between overlay nodes)
+    const uint32_t* st = tab + (size_t)(si * NO + ti) * rfl((uint32_t)t_ovrow(S, NN));
+    uint32_t e = 0u;
+    if (ok && lane < deg) e = st[r0 + lane];
+    uint32_t c_prev = 0u;
+    if (ok && has_prev && pu < NN) {
+        const uint32_t p0 = rfl((uint32_t)t_ovrow(S, pu));
+        if (pa < rfl((uint32_t)t_ovrow(S, pu + 1)) - p0) c_prev = rfl(st[p0 + pa]) >> 24;
+    }
+    if (c_prev != 0u) {
+        const uint64_t m = __ballot(lane < deg && (e >> 24) == c_prev);
+        if (m) return (int)__builtin_ctzll(m);
+    }
+    uint32_t c[4] = { rfl(d), 0u, H.episode, 3u };
+    uint32_t k0 = S.lv.seed_lo(), k1 = S.gid;
+    asm volatile("" : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]), "+v"(k0), "+v"(k1));
+    philox4x32_10(c, k0, k1);
+    const uint32_t c1 = rfl(c[1]);
+    const uint32_t ps = wave_scan_u32(e & 0xffffffu);
+    const uint32_t W = rdl(ps, 63u);
+    if (W == 0u) return (int)(uint32_t)(((uint64_t)c1 * deg) >> 32);
+    const uint32_t u = (uint32_t)(((uint64_t)c1 * W) >> 32);
+    return (int)__builtin_ctzll(__ballot(ps > u));
+}
+
 template <int FS, int LS>
 __device__ __forceinline__ void stage_in(unsigned char* lds, const KParams& P, int r, int lane, Regs<FS, LS>& R) {
     CLayout& LC = *(CLayout*)P.lay;
@@ -2843,7 +2931,7 @@ __device__ __forceinline__ bool spare_restart(const KParams&, Sim&, RS&, int, ui
 // needs an external action, or the end of the episode; publish the outputs.
 // ---------------------------------------------------------------------------
 // EXPL: the fused policy's action goes through explore_action (1) or smart_explore_action (2)
-// at both decision sites
+// at both decision sites; 3: the action is stoch_action's (P.stoch_tab) and no table is read
 // MB: mlp_action_reg's batch (the memory-resident engine passes 0)
 // LQ: the MLP is one of the reduced DQN-buffer models (lightq_action_reg with P.lq_dims;
 // register-resident instances of their own)
@@ -2874,7 +2962,14 @@ __device__ __forceinline__ uint32_t event_loop(const KParams& P, Sim& S, RS& R, 
         if (table_mode) {
             uint32_t pn = u_ld32(&S.h->pend_node), pd = u_ld32(&S.h->pend_ent[1]);
             int a;
-            if (!mlp_mode) {
+            if constexpr (EXPL == 3) {
+                // (the previous decision's record through the pending entry, as the arrival found it)
+                const uint32_t px = u_ld32(&S.h->pend_ent[0]), pdec = u_ld32(&S.h->pend_dec);
+                const int32_t pp = ent_type(px) == T_FRESH ? -1 : (int32_t)(pdec - relay_dist(S, pdec, px));
+                const uint32_t w6 = pp < 0 ? 0u : record_word(S, (uint32_t)pp, 24);
+                const uint32_t w7 = pp < 0 ? 0u : record_word(S, (uint32_t)pp, 28);
+                a = stoch_action(S, H, P.stoch_tab, pdec, pn, pd, px, pp, w6 & 255u, w7 & 255u);
+            } else if (!mlp_mode) {
                 a = table_action(S, pn * NN + pd);
             } else if constexpr (RS::kMem) {
                 MlpPre1 M0;                              // (no arrival came before: nothing prefetched)
@@ -2953,7 +3048,8 @@ __device__ __forceinline__ uint32_t event_loop(const KParams& P, Sim& S, RS& R, 
             if (need) {
                 if (table_mode) {
                     int a;
-                    if (!mlp_mode) a = table_action(S, D.v * NN + D.dst);
+                    if constexpr (EXPL == 3) a = stoch_action(S, H, P.stoch_tab, D.d, D.v, D.dst, D.x, D.prev, D.last, D.pact & 255u);
+                    else if (!mlp_mode) a = table_action(S, D.v * NN + D.dst);
                     else if constexpr (RS::kMem) a = mlp_action_mem<true>(S, D.v, D.obs, Mp);
                     else if constexpr (LQ) a = lightq_action_reg<MB>(S, D.v, D.obs, P.lq_dims);
                     else a = mlp_action_reg<MB>(S, D.v, D.obs, Mp);

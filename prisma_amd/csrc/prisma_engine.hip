@@ -124,6 +124,8 @@ const void* prisma_pick_step_explore_lightq(int fs, int ls, bool tun);
 const void* prisma_pick_step_smart(int fs, int ls, bool tun);
 const void* prisma_pick_step_smart_mlp(int fs, int ls, bool tun);
 const void* prisma_pick_step_smart_lightq(int fs, int ls, bool tun);
+// ... and the ones with stochastic multipath routing (prisma_run_stochastic) in prisma_engine_stoch.hip
+const void* prisma_pick_step_stoch(int fs, int ls, bool tun);
 static const void* pick_step_ctrl(int fs, int ls, bool tun) { return pick_step<true, false>(fs, ls, tun); }
 
 template <int FS, int LS> const void* reset_kernel() { return (const void*)prisma_reset_kernel_t<FS, LS>; }
@@ -341,6 +343,7 @@ struct prisma_env {
     const void* k_smart = nullptr;       // history-weighted exploration (prisma_run_explore_smart): register
     const void* k_smart_mlp = nullptr;   // engine without the ctrl paths only
     const void* k_smart_lightq = nullptr;
+    const void* k_stoch = nullptr;       // stochastic multipath routing (prisma_run_stochastic): likewise
     std::vector<int32_t> ovrow;          // [N + 1] overlay CSR rows by underlay id (prisma_action_history_layout)
     float* d_lq_rp = nullptr;            // their interleaved weights (sized for the largest, DQN_LITE)
     float* d_mlp_rp = nullptr;           // interleaved DQN-buffer layers 2-4 (prisma_run, mode 4)
@@ -1157,6 +1160,7 @@ extern "C" int prisma_create(const prisma_topology_t* topo, const prisma_params_
             e->k_smart = prisma_pick_step_smart(L.FS, L.LS, L.tunnels != 0u);
             e->k_smart_mlp = prisma_pick_step_smart_mlp(L.FS, L.LS, L.tunnels != 0u);
             e->k_smart_lightq = prisma_pick_step_smart_lightq(L.FS, L.LS, L.tunnels != 0u);
+            e->k_stoch = prisma_pick_step_stoch(L.FS, L.LS, L.tunnels != 0u);
         }
         e->kinfo.ctrl = ctrl ? 1u : 0u;
         e->kinfo.relay_ip = (L.tunnels && !ctrl) ? 1u : 0u;
@@ -1182,6 +1186,7 @@ extern "C" int prisma_create(const prisma_topology_t* topo, const prisma_params_
         (void)hipFuncSetAttribute(e->k_smart_mlp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_mlp_bytes);
     if (e->k_smart_lightq)
         (void)hipFuncSetAttribute(e->k_smart_lightq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_mlp_bytes);
+    if (e->k_stoch) (void)hipFuncSetAttribute(e->k_stoch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bytes);
     *out = e;
     return PRISMA_OK;
 }
@@ -1363,6 +1368,31 @@ extern "C" int prisma_run_explore_smart(prisma_env_t* e, int32_t policy, const v
         return set_err(PRISMA_ERR_ARG, "prisma_run_explore_smart: action_hist must be a device uint32 [n_replicas][T] "
                                        "array and hist_words = n_replicas * T (prisma_action_history_layout)");
     return run_fused(e, policy, policy_data, max_hops, explore_thr, action_hist, stream);
+}
+
+extern "C" int prisma_run_stochastic(prisma_env_t* e, const uint32_t* tab, uint64_t tab_words, int32_t max_hops,
+                                     void* stream) {
+    if (!e) return set_err(PRISMA_ERR_ARG, "null env");
+    // as the exploring instances: the register-resident engine without the ctrl paths only
+    if (e->lay.mem)
+        return set_err(PRISMA_ERR_CONFIG, "prisma_run_stochastic: the memory-resident engine has no instances with "
+                                          "stochastic routing");
+    if (e->kinfo.ctrl || !e->k_stoch)
+        return set_err(PRISMA_ERR_CONFIG, "prisma_run_stochastic: this env runs the step kernels with the ctrl paths "
+                                          "(train, notify_dest, ns-3 streams, or a tunnelled overlay with log_capacity "
+                                          ">= 2^18), which have no instances with stochastic routing");
+    const uint64_t NO = (uint64_t)e->lay.NO;
+    if (!tab || tab_words != NO * NO * (uint64_t)e->ovrow.back())
+        return set_err(PRISMA_ERR_ARG, "prisma_run_stochastic: tab must be a device uint32 [NO][NO][T] array and "
+                                       "tab_words = NO * NO * T (prisma_action_history_layout)");
+    if (!e->reset_done) return set_err(PRISMA_ERR_STATE, "prisma_reset must be called first");
+    if (max_hops < 1) return set_err(PRISMA_ERR_ARG, "max_hops must be >= 1");
+    KParams P = base_params(e);
+    P.mode = 2;                          // a fused run: the episode restart and the hop budget as prisma_run's
+    P.max_hops = max_hops;
+    P.stoch_tab = tab;
+    int rc = launch(e, e->k_stoch, P, stream);
+    return rc ? rc : auto_reset(e, stream);
 }
 
 extern "C" int prisma_read_counters(prisma_env_t* e, prisma_counters_t* host_out, void* stream) {

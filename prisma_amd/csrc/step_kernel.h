@@ -54,7 +54,8 @@ __device__ unsigned long long g_wave_times[4 * 65536];
 #endif
 
 // The kernel body, shared by the kernel templates below (EXPL_: 0 greedy, 1 uniform
-// exploration, 2 history-weighted exploration; FUSED_: the fused-only table instances).  A macro
+// exploration, 2 history-weighted exploration, 3 stochastic multipath routing; FUSED_: the fused-only
+// table instances).  A macro
 // rather than an inlined function, for the reason given above, and rather than one more template
 // parameter, so the existing instances keep their symbol names.
 //
@@ -96,6 +97,7 @@ __device__ unsigned long long g_wave_times[4 * 65536];
         asm volatile("" : "+s"(kp));                                                                    \
         KParams P2 = *kp;                                                                               \
         if (EXPL_ == 2) P2.action_hist = rfl_ptr(P2.action_hist);                                       \
+        if (EXPL_ == 3) P2.stoch_tab = rfl_ptr(P2.stoch_tab);                                           \
         if (spare_restart(P2, S, R, r, done, budget)) {                                                 \
             S.prio_base = done;                                                                         \
             event_loop<MLP, StepOcc<FS, LS>::mlp_batch, EXPL_, LQ, FUSED_>(P2, S, R, r, budget);        \
@@ -133,6 +135,18 @@ prisma_step_kernel_fused_t(KParams P) {
     PRISMA_STEP_KERNEL_BODY(0, true)
 }
 
+// STOCH: the instances of prisma_run_stochastic (engine_core.h stoch_action), without the ctrl
+// paths and fused-only: no table is read and no external action taken, so event_loop's FUSED
+// folding applies to the tunnelled ones as well.  The parameters end in TUN, CTRL as the fused
+// template's do; only CTRL = false is instantiated.
+template <int FS, int LS, bool TUN, bool CTRL>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(StepOcc<FS, LS>::waves)))
+prisma_step_kernel_stoch_t(KParams P) {
+    static_assert(!CTRL, "the stoch instances carry no ctrl paths");
+    constexpr bool MLP = false, LQ = false;
+    PRISMA_STEP_KERNEL_BODY(3, true)
+}
+
 // instantiations: flow slots FS in {1,2,4,8} (F <= 512), link slots LS in {1,2,4} (L <= 256)
 template <int FS, int LS, bool CTRL, bool MLP, bool EXPL = false, bool LQ = false> const void* step_kernel(bool tun) {
     static_assert(!(EXPL && CTRL), "the exploring instances carry no ctrl paths");
@@ -148,7 +162,7 @@ template <int FS, int LS, bool CTRL, bool MLP, bool EXPL = false, bool LQ = fals
 // prisma_engine_explore_mlp.hip (EXPL, without the ctrl paths), prisma_engine_lightq.hip and
 // prisma_engine_explore_lightq.hip (LQ, without the ctrl paths), prisma_engine_smart.hip,
 // prisma_engine_smart_mlp.hip and prisma_engine_smart_lightq.hip (SMART, without the ctrl paths),
-// prisma_engine_fused.hip (FUSED tables, without the ctrl paths)
+// prisma_engine_fused.hip (FUSED tables, without the ctrl paths), prisma_engine_stoch.hip (STOCH)
 template <bool CTRL, bool MLP, bool EXPL = false, bool LQ = false>
 static const void* pick_step(int fs, int ls, bool tun) {
 #ifdef PRISMA_DEV_HEADLINE
@@ -196,6 +210,21 @@ static const void* pick_step_smart(int fs, int ls, bool tun) {
     if (fs == F_ && ls == L_)                                                                           \
         return tun ? (const void*)prisma_step_kernel_smart_t<F_, L_, MLP, true, LQ>                     \
                    : (const void*)prisma_step_kernel_smart_t<F_, L_, MLP, false, LQ>;
+    PK(1, 1) PK(1, 2) PK(1, 4) PK(2, 1) PK(2, 2) PK(2, 4) PK(4, 1) PK(4, 2) PK(4, 4) PK(8, 1) PK(8, 2) PK(8, 4)
+#undef PK
+    return nullptr;
+#endif
+}
+
+template <bool CTRL>
+static const void* pick_step_stoch(int fs, int ls, bool tun) {
+#ifdef PRISMA_DEV_HEADLINE
+    return nullptr;
+#else
+#define PK(F_, L_)                                                                                      \
+    if (fs == F_ && ls == L_)                                                                           \
+        return tun ? (const void*)prisma_step_kernel_stoch_t<F_, L_, true, CTRL>                        \
+                   : (const void*)prisma_step_kernel_stoch_t<F_, L_, false, CTRL>;
     PK(1, 1) PK(1, 2) PK(1, 4) PK(2, 1) PK(2, 2) PK(2, 4) PK(4, 1) PK(4, 2) PK(4, 4) PK(8, 1) PK(8, 2) PK(8, 4)
 #undef PK
     return nullptr;

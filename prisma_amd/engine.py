@@ -104,7 +104,7 @@ class _Plan(C.Structure):
 
 EXPORTS = [
     "prisma_abi_version", "prisma_last_error", "prisma_build_id", "prisma_create", "prisma_reset", "prisma_step", "prisma_run",
-    "prisma_run_explore", "prisma_action_history_layout", "prisma_run_explore_smart",
+    "prisma_run_explore", "prisma_action_history_layout", "prisma_run_explore_smart", "prisma_run_stochastic",
     "prisma_read_counters", "prisma_counters_device", "prisma_log_view", "prisma_copy_log",
     "prisma_copy_counters", "prisma_gather_records", "prisma_state_bytes", "prisma_plan", "prisma_destroy",
     "prisma_compact_pending", "prisma_expand_actions", "prisma_kernel_info", "prisma_ingest_transitions",
@@ -155,6 +155,8 @@ def load_library(path: str = None):
     L.prisma_run_explore_smart.restype = C.c_int
     L.prisma_run_explore_smart.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                            C.c_uint64, C.c_void_p]
+    L.prisma_run_stochastic.restype = C.c_int
+    L.prisma_run_stochastic.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p]
     L.prisma_read_counters.restype = C.c_int
     L.prisma_read_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.prisma_counters_device.restype = C.c_int
@@ -456,6 +458,32 @@ class PrismaEngine:
             return
         _check(_lib.prisma_run_explore(self.h, kind, self._policy_keep.data_ptr(), int(max_hops),
                                        self._thr_keep.data_ptr(), _stream_handle(stream)))
+
+    def run_stochastic(self, tab, max_hops: int, stream=None):
+        """Fused stochastic multipath routing, the reference's "opt" agent (prisma_run_stochastic;
+        prisma_amd/optrouting.py restates its rule): every replica executes up to max_hops hops.
+
+        tab: a contiguous int32 or uint32 [n_overlay, n_overlay, T] tensor on this engine's device,
+        the table optrouting.pack_routing builds (T = action_history_layout()[1]); the kernels read
+        its bits as uint32.  It is read during the launch: keep it unchanged until the launch is done
+        (the engine holds a reference).  The register-resident engine without the ctrl paths only."""
+        import torch
+        no, total = self.topo.n_overlay, self.action_history_layout()[1]
+        if (not torch.is_tensor(tab) or tab.device != self.torch_device
+                or tab.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32))
+                or tuple(tab.shape) != (no, no, total) or not tab.is_contiguous()):
+            raise PrismaError(f"prisma_run_stochastic: tab must be a contiguous int32 / uint32 [{no}, {no}, {total}] "
+                              f"tensor on {self.torch_device} (optrouting.pack_routing)")
+        self._policy_keep = tab
+        _check(_lib.prisma_run_stochastic(self.h, tab.data_ptr(), tab.numel(), int(max_hops), _stream_handle(stream)))
+
+    def stochastic_table(self, routing):
+        """optrouting.pack_routing(topo, routing) as a device tensor for run_stochastic (int32 storage
+        of the uint32 words)."""
+        import torch
+        from . import optrouting
+        tab = optrouting.pack_routing(self.topo, routing)
+        return torch.from_numpy(tab.view(np.int32)).to(self.torch_device)
 
     def _explore_thr(self, explore):
         """Epsilons -> the device thresholds of prisma_run_explore (explore.thresholds' rule:

@@ -142,7 +142,13 @@ class VecRoutingEnv:
 
     def run(self, table: torch.Tensor, max_hops: int, explore=None, model: str = "buffer", action_history=None):
         """Fused launch (PrismaEngine.run); explore: epsilons of an epsilon-greedy rollout;
-        model: the kind of a packed fp32 policy."""
+        model: the kind of a packed fp32 policy, or "opt": `table` is the packed routing table of
+        the stochastic multipath agent (PrismaEngine.run_stochastic, optrouting.pack_routing)."""
+        if model == "opt":
+            if explore is not None or action_history is not None:
+                raise ValueError("model='opt' draws by its routing matrix: no explore / action_history")
+            self.engine.run_stochastic(table, max_hops)
+            return
         self.engine.run(table, max_hops, explore=explore, model=model, action_history=action_history)
 
     def counters(self) -> np.ndarray:
