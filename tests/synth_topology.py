@@ -1,6 +1,8 @@
 """Synthetic topologies that reach every (flow_slots, link_slots) instance of the register-resident
 step kernel at its slot boundaries, and the case matrix tests/test_instance_matrix.py (CPU: the
-plan and the oracle's own run) and tests/test_gpu_instances.py (GPU parity) both import.
+plan and the oracle's own run) and tests/test_gpu_instances.py (GPU parity) both import; then the
+same for the memory-resident engine's 64-ary event tree (MEMORY_CASES, at the end of the file:
+tests/test_mem_instance_matrix.py and tests/test_gpu_mem_instances.py).
 
 numpy only, seeded, deterministic.  On an identity overlay the engine numbers the 2m directed
 switch links first (CSR order) and then one access link per node, so it has 2m + n links: link
@@ -225,7 +227,8 @@ def case_params(name, **kw):
 
 
 def last_switch_slot(topo):
-    """The last register slot that holds a switch link of an identity overlay."""
+    """The last register slot (the memory-resident engine: 64-leaf link block) that holds a
+    switch link of an identity overlay."""
     return (topo.n_links - 1) >> 6
 
 
@@ -249,3 +252,169 @@ def dcache_bytes(name, **kw):
     a = engine.plan(build(name), case_params(name, **kw))
     b = engine.plan(build(name), case_params(name, rng="ns3", **kw))
     return a["lds_state_bytes"] - (b["lds_state_bytes"] - RNG_BYTES)
+
+
+# ---- the memory-resident engine's matrix --------------------------------------------------
+# Its event tree is 64-ary: 64 link leaves (Lk = n_links + n_nodes of them) per link block, 64 flow
+# leaves (FG = the flows, plus one leaf the big-signalling generators share) per flow block, 64 flow
+# blocks per flow group; the n_lb link blocks and the flow groups are the n_top <= 64 lanes of the
+# top level (prisma_engine.hip layout_mem).  tests/test_mem_instance_matrix.py (CPU: the plan and
+# the oracle's own run) and tests/test_gpu_mem_instances.py (GPU parity) import what follows.
+def circulant(n, k, chords, f, seed, rate):
+    """Identity overlay on a ring of n nodes, each joined to its k nearest nodes on either side,
+    plus `chords` chords of offset k + 1 from nodes 0 .. chords - 1: 2 (n k + chords) switch links."""
+    rng = np.random.default_rng([seed, n, k, chords, f])
+    adj = np.zeros((n, n), dtype=np.int64)
+    v = np.arange(n)
+    for d in range(1, k + 1):
+        adj[v, (v + d) % n] = adj[(v + d) % n, v] = 1
+    c = np.arange(chords)
+    adj[c, (c + k + 1) % n] = adj[(c + k + 1) % n, c] = 1
+    tm = np.zeros((n, n), dtype=object)
+    for a, b in _pick_flows(range(n), f, rng):
+        tm[a, b] = int(rate)
+    return Topology.from_matrices(adj, tm, name=f"circ{n}_{k}_{chords}_{f}")
+
+
+def slow_tail(n, m, f, seed, rate, tail_rate):
+    """synth's graph and flows, but the last flow (alone in its flow block when f = 64 j + 1) sends
+    at `tail_rate`."""
+    rng = np.random.default_rng([seed, n, m, f])
+    adj = _tree_plus_edges(n, m, rng)
+    tm = np.zeros((n, n), dtype=object)
+    flows = _pick_flows(range(n), f, rng)
+    for a, b in flows:
+        tm[a, b] = int(rate)
+    tm[flows[-1]] = int(tail_rate)
+    return Topology.from_matrices(adj, tm, name=f"slow{n}_{m}_{f}")
+
+
+def line(n, flows, seed, rate):
+    """A path of n nodes with the given (src, dst) flows; the seed is not used."""
+    adj = np.zeros((n, n), dtype=np.int64)
+    v = np.arange(n - 1)
+    adj[v, v + 1] = adj[v + 1, v] = 1
+    tm = np.zeros((n, n), dtype=object)
+    for a, b in flows:
+        tm[a, b] = int(rate)
+    return Topology.from_matrices(adj, tm, name=f"line{n}")
+
+
+def bfs_next_hop_table(topo):
+    """[N, N] uint8 action table of an identity overlay from the topology's own BFS routing
+    (route_tables: the lowest-numbered neighbour one hop nearer).  sp_next_hop_table's bidirectional
+    search per pair is slow at 256 nodes; parity only needs the same table on both sides."""
+    assert topo.identity and topo.max_deg <= 255
+    rank = np.cumsum(topo.adjacency, axis=1) - 1                     # neighbour v is action rank[u, v] of u
+    table = np.take_along_axis(rank, np.maximum(topo.next_hop, 0).astype(np.int64), axis=1)
+    np.fill_diagonal(table, 0)
+    return np.ascontiguousarray(table, dtype=np.uint8)
+
+
+def tree_shape(topo, big_signaling=0):
+    """(Lk, FG, n_lb, n_fb, n_top) of an identity overlay by layout_mem's formulas; with big
+    signalling the generators (one per flow between neighbours) share one more flow leaf."""
+    lk = topo.n_links + topo.n_nodes
+    n_gen = int(topo.adjacency[topo.flow_src, topo.flow_dst].sum()) if big_signaling else 0
+    fg = topo.n_flows + int(n_gen > 0)
+    n_lb, n_fb = (lk + 63) // 64, (fg + 63) // 64
+    return lk, fg, n_lb, n_fb, n_lb + (n_fb + 63) // 64
+
+
+def mem_lds_state_bytes(shape, obs_width, ns3=False):
+    """The LDS part of the memory-resident engine's state image: header, counters, pending
+    observation, flow block minima, top-level image, link leaf keys and kinds (16-B aligned each)."""
+    lk, _, _, n_fb, n_top = shape
+    a16 = lambda b: (b + 15) & ~15
+    return 128 + 160 + a16(4 * obs_width) + 16 * n_fb + 16 * n_top + a16(8 * lk) + a16(lk) + (RNG_BYTES if ns3 else 0)
+
+
+# name: builder and its arguments, builder seed, per-flow rate(s), hops per replica (None: to the
+# episode's end), log capacity, the expected tree shape (Lk, FG, n_lb, n_fb, n_top), engine params
+# beyond the common ones.  The rates of the large cases are set so that the hops span 3 ping rounds.
+def _m(kind, args, shape, hops=H, bseed=SEED, rate=None, log=LOG, **params):
+    return dict(kind=kind, args=args, seed=bseed, rate=rate, hops=hops, log=log, shape=shape, params=params)
+
+
+_BSIG = dict(train=1, signaling_type="NN", big_signaling=1, sync_step_s=0.25)
+_MEM_IDENTITY_SHAPES = {
+    "l64_f64": (64, 64, 1, 1, 2), "l65_f65": (65, 65, 2, 2, 3), "l64_f129": (64, 129, 1, 3, 2),
+    "l64_f257": (64, 257, 1, 5, 2), "l128_f64": (128, 64, 2, 1, 3), "l129_f128": (129, 128, 3, 2, 4),
+    "l128_f256": (128, 256, 2, 4, 3), "l128_f512": (128, 512, 2, 8, 3), "l129_f64": (129, 64, 3, 1, 4),
+    "l256_f65": (256, 65, 4, 2, 5), "l256_f129": (256, 129, 4, 3, 5), "l256_f512": (256, 512, 4, 8, 5),
+    "l256d_f130": (256, 130, 4, 3, 5), "l40_f100": (40, 100, 1, 2, 2), "l100_f128": (100, 128, 2, 2, 3),
+}
+# every IDENTITY case forced onto the memory-resident engine: Lk and FG at 64, 65, 128, 129, 256, 512
+MEM_IDENTITY = {n: _m(c["kind"], c["args"], _MEM_IDENTITY_SHAPES[n], rate=c["rate"], **c["params"])
+                for n, c in IDENTITY.items()}
+MEM_NEW = {
+    # 9 flow blocks, flow 512 alone in the last
+    "m_f513": _m("synth", MEMORY_ONLY, (70, 513, 2, 9, 3), hops=6000),
+    # one flow group exactly full (64 blocks) | flow 4096 alone in block 64, alone in group 1; about
+    # one packet per flow in 16 000 hops: engine seed 110 is one under which flow 4096 sends on every
+    # replica (found by a CPU search of seeds 105-112)
+    "m_f4096": _m("synth", (66, 100, 4096), (266, 4096, 5, 64, 6), hops=16000, rate=4000, log=32768),
+    "m_f4097": _m("synth", (66, 100, 4097), (266, 4097, 5, 65, 7), hops=16000, rate=4000, log=32768, seed=110),
+    # 256 nodes, 3 776 switch links: 63 link blocks (59 with switch links, 4 with the access links)
+    # and one flow group in lane 63 of the top level, whose last flow block holds 24 flows
+    "m_top64": _m("circulant", (256, 7, 96, 600), (4032, 600, 63, 10, 64), hops=12000, rate=15000, log=16384),
+    # 60 link blocks and 4 flow groups, the last with one block: lanes 60-63
+    "m_top64_groups": _m("circulant", (256, 7, 0, 12352), (3840, 12352, 60, 193, 64), hops=16000, rate=900,
+                         log=32768),
+    # big signalling: the generators' leaf (FG = flows + 1) alone in block 1 | alone in group 1
+    "m_bsig65": _m("synth", (22, 21, 64), (64, 65, 1, 2, 2), **_BSIG),
+    "m_bsig4097": _m("synth", (66, 100, 4096), (266, 4097, 5, 65, 7), hops=16000, rate=4000, log=32768, **_BSIG),
+    # flows 0-63 send every 0.5 s on average, flow 64 (block 1's only leaf) every 7 s: when its send
+    # re-reduces block 1, the block's only key is more than 2^32 ns ahead of the clock (the saturated
+    # reduction of fblock_min_cached, beside a busy block 0).  To the end of a 40-s episode; engine seed 113: flow 64
+    # has two sends that far apart on every replica, in the table's run and within the first 16 000
+    # hops of the DQN-buffer MLP's (seed 21), whose routes are longer (CPU search of seeds 105-120)
+    "m_slow65": _m("slow_tail", (12, 20, 65), (52, 65, 1, 2, 2), hops=None, rate=(8192, 585), log=32768,
+                   sim_time_s=40.0, seed=113),
+    # m_f4097 with a flow 4096 that sends every 7 s on average: its start event (within the first
+    # second) schedules its first send more than 2^32 ns ahead, the only key of block 64 and of group
+    # 1 (fgroup_min's saturated reduction over a partial group, next to 4 096 busy flows).  Engine
+    # seed 115: so on every replica (CPU search of seeds 105-124); flow 4096 never sends in the run
+    "m_g1slow": _m("slow_tail", (66, 100, 4097), (266, 4097, 5, 65, 7), hops=16000, rate=(4000, 585), log=32768,
+                   seed=115),
+    # m_bsig65 with a 5-s period: the generators' leaf, block 1's only one, is re-armed more than
+    # 2^32 ns ahead at their start, and fires once before the 6-s episode ends
+    "m_bsig65_slow": _m("synth", (22, 21, 64), (64, 65, 1, 2, 2), hops=None, rate=20000, log=16384,
+                        **dict(_BSIG, sync_step_s=5.0)),
+    # three flows that send every 13.7 s on average and a ping every 7 s: between ping rounds every
+    # key of the top level and the ping timer are more than 2^32 ns ahead (select_event's saturated
+    # reduction, on either engine).  To the end of a 60-s episode; engine seed 108: every replica has
+    # a ping round with no record from 0.5 s before it to the next (CPU search of seeds 105-116)
+    "m_idle": _m("line", (4, ((0, 3), (3, 0), (1, 2))), (10, 3, 1, 1, 2), hops=None, rate=300,
+                 sim_time_s=60.0, ping_interval_s=7.0, seed=108),
+}
+RUN_TO_END = 10 ** 6                   # hops of the cases that run to the episode's end (hops=None)
+MLP_SEED = 21                          # StackedQNet(topo, "buffer", seed=) of the MLP runs
+SLOW_MLP_HOPS = 16000                  # m_slow65 under the MLP: about 16 s of the episode
+MEMORY_CASES = {**MEM_IDENTITY, **MEM_NEW}
+
+
+@functools.lru_cache(maxsize=None)
+def build_mem(name):
+    c = MEMORY_CASES[name]
+    fn = {"synth": synth, "circulant": circulant, "slow_tail": slow_tail, "line": line}[c["kind"]]
+    rate = c["rate"] if isinstance(c["rate"], tuple) else (c["rate"],)
+    return fn(*c["args"], c["seed"], *rate)
+
+
+@functools.lru_cache(maxsize=None)
+def mem_table(name):
+    return bfs_next_hop_table(build_mem(name))
+
+
+def mem_params(name, **kw):
+    """engine_params of a memory case: case_params' conventions (R = 3 replicas from replica_base 7,
+    a 6-s episode), the case's log, the memory-resident engine, the case's overrides, the caller's."""
+    from prisma_amd.config import engine_params
+    from prisma_amd.engine import PRISMA_ENGINE_MEMORY
+    c = MEMORY_CASES[name]
+    args = dict(sim_time_s=SIM_TIME_S, replica_base=REPLICA_BASE, log_capacity=c["log"], seed=100 + SEED,
+                engine=PRISMA_ENGINE_MEMORY)
+    args.update(c["params"])
+    args.update(kw)
+    return engine_params(build_mem(name), **args)
