@@ -2253,8 +2253,17 @@ __device__ __forceinline__ int on_arrive(const Sim& S, RS& R, Hot& H, uint32_t l
         // and consumed after the link update and the observation, which do
         // not depend on it (and only on this path, so no load is ever left
         // in flight across loop iterations).
-        // (A fresh packet loads and ignores some record of its own log: the
-        // load and its consumption are unconditional on this path.)
+        // A fresh packet (off an access link) has no previous record: everything
+        // it needs is in its ring entry.  On the register-resident engine a uniform
+        // branch on the entry's type skips the two loads, and their consumers all
+        // stand in the relay branch below, so a fresh arrival issues no load and
+        // waits for none (skip_fresh).  Two instance sets keep the unconditional
+        // load, of the slot the fresh entry's dst / parity / uid bits happen to
+        // name, and ignore it: the memory-resident engine (the branch cost config 5
+        // 1.3 % in alternating A/B) and the tunnelled --train instances (one of
+        // them would spill 4 VGPRs).  profiles/fresh_arrival/README.md.
+        const bool fresh = type == T_FRESH;
+        const bool skip_fresh = !S.mem && !(S.tun && S.ctrl);      // (compile-time constants)
         const uint32_t d = H.dec;
         const uint32_t dist = relay_dist(S, d, x);
         // The previous decision is log_capacity or more decisions old: its record has been
@@ -2270,8 +2279,12 @@ __device__ __forceinline__ int on_arrive(const Sim& S, RS& R, Hot& H, uint32_t l
             return 0;
         }
         const unsigned char* pr = S.logrep + (size_t)((d - dist) & (L.log_cap() - 1)) * L.rec_bytes();
-        const uint4 ph = *(const uint4*)pr;
-        const uint2 pw = *(const uint2*)(pr + 24);
+        uint4 ph = make_uint4(0u, 0u, 0u, 0u);
+        uint2 pw = make_uint2(0u, 0u);
+        if (!skip_fresh || !fresh) {
+            ph = *(const uint4*)pr;
+            pw = *(const uint2*)(pr + 24);
+        }
         if constexpr (PRE) {                                        // the decision's weights ride along
             if (S.ctrl) {
                 mlp_preload_node(Mpre, S, v, 0u, false);
@@ -2317,14 +2330,18 @@ __device__ __forceinline__ int on_arrive(const Sim& S, RS& R, Hot& H, uint32_t l
         if (!S.mem) { r0 = t_ovrow(S, v); deg = t_ovrow(S, v + 1) - r0; }
         const uint32_t obs_links = S.mem ? obs_early : observe_links(S, R, H, v, ns_to_sec(H.now), r0, deg);
         D.r0 = r0; D.deg = deg;
-        const int64_t t_prev = mk64(rfl(ph.x), rfl(ph.y));
-        const uint32_t uid_prev = rfl(ph.z), w_prev = rfl(pw.x);
+        int64_t t_prev = 0;
+        uint32_t uid_prev = 0u, w_prev = 0u;
+        if (!skip_fresh) {                                          // (the record is waited for here)
+            t_prev = mk64(rfl(ph.x), rfl(ph.y));
+            uid_prev = rfl(ph.z); w_prev = rfl(pw.x);
+        }
         if (S.mem) TP1(3);
         TP2(3);
         double reward = 0.0;
         int32_t prev = -1;
-        uint32_t dst, start, uid, last = 0u;
-        if (type == T_FRESH) {
+        uint32_t dst, start, uid, last = 0u, pact = 0u;
+        if (fresh) {
             // first notification: destination from the flow, uid and start
             // second rebuilt from their low bits (the packet left its app less
             // than 1 s and fewer than 2^20 injections ago)
@@ -2335,6 +2352,11 @@ __device__ __forceinline__ int on_arrive(const Sim& S, RS& R, Hot& H, uint32_t l
             uid = lu - ((lu - f_uid(x)) & kUidMask);
         } else {
             prev = (int32_t)(d - dist);                             // (dist < log_cap: checked above)
+            if (skip_fresh) {                                       // the record is first waited for here
+                t_prev = mk64(rfl(ph.x), rfl(ph.y));
+                uid_prev = rfl(ph.z); w_prev = rfl(pw.x);
+            }
+            pact = rfl(pw.y);
             uid = uid_prev;
             dst = (w_prev >> 8) & 255u;
             start = w_prev >> 16;
@@ -2360,7 +2382,7 @@ __device__ __forceinline__ int on_arrive(const Sim& S, RS& R, Hot& H, uint32_t l
         // packet to the last hop, unless this node is the packet's source (:303-306)
         const uint32_t echo = (S.ctrl && L.train() && v != ent_src(x, v)) ? PEND_ECHO : 0u;
         D.x = x; D.dst = dst; D.start = start; D.uid = uid; D.v = v; D.d = d; D.reward = reward; D.prev = prev;
-        D.obs = o; D.flags = echo; D.last = last; D.ttl = ttl; D.pact = rfl(pw.y);
+        D.obs = o; D.flags = echo; D.last = last; D.ttl = ttl; D.pact = skip_fresh ? pact : rfl(pw.y);
         if (dst == v) {                                             // getGameOver
             write_record(S, H, d, reward, uid, prev, v, dst, start, -1, PRISMA_ST_DESTINATION, o, ttl);
             if (!fused && S.ctrl && L.notify_dest()) {              // the agent is notified (done=True)
