@@ -340,6 +340,11 @@ struct Sim {
     bool mem;                               // memory-resident engine (compile-time constant, folded)
     bool ctrl;                              // --train echo / notify_dest paths compiled in (constant)
     bool mlp_inst;                          // an in-kernel MLP instance (event_loop's MLP, constant)
+    bool lanel;                             // lane-resident link handlers (lane_links_bind; constant)
+    // ... and their per-lane constants of link `lane`: ring offset | capacity << 16, tx time of a
+    // data / ping entry and the propagation delay (low 32 bits), the admission limit (bytes on a
+    // switch link, packets on an access link) and the access-link mask (all ones / 0)
+    uint32_t lk_rinfo, lk_txd, lk_txp, lk_prop, lk_lim, lk_acc;
     // memory-resident engine: variable-size topology arrays (scalar loads)
     const CAS int32_t* m_rowptr;
     const CAS int32_t* m_ldst;
@@ -403,6 +408,8 @@ __device__ inline void sim_bind(Sim& S, const LV& L, unsigned char* lds, const u
     S.mem = false;
     S.ctrl = true;
     S.mlp_inst = false;
+    S.lanel = false;
+    S.lk_rinfo = 0; S.lk_txd = 0; S.lk_txp = 0; S.lk_prop = 0; S.lk_lim = 0; S.lk_acc = 0;
     S.lrec = nullptr;
     S.prio_total = 0; S.prio_base = 0; S.prio_next = kPrioNever; S.prio_shift = 31u;
 }
@@ -825,6 +832,139 @@ __device__ __forceinline__ bool ring_store_needed(const Sim& S, const LinkV& k) 
     return true;
 }
 
+// ---- lane-resident link handlers (register-resident engine, LS = 1: link l lives in lane l)
+// The handlers below pull one link's fields out of their lane with ~8 v_readlane, run the FIFO
+// and transmitter arithmetic on the scalar unit -- with two dependent scalar loads (rinfo, ltx)
+// -- and write the fields back through 8 compare/selects.  At 4 waves per SIMD the headline is
+// bound by instruction issue with the scalar unit the busy side (one per CU against four SIMDs;
+// DESIGN.md §9), so the instances with S.lanel run the same arithmetic in the fields' own lane
+// instead: every lane computes the update of ITS link as if the packet were sent on it, and
+// only the owner lane (lane == l) commits.  The per-link constants sit in VGPRs, loaded once
+// before the event loop (lane_links_bind) and opaque to the optimiser, so no handler loads a
+// constant.  What stays scalar: the sequence numbers (H.seq), the event count and the error
+// flags, which link_send_lane takes from one status word read back with a single v_readlane.
+// PRISMA_LANE_LINKS (build switch for the A/B variants of profiles/lane_links/): bit 0 the
+// completion handler, bit 1 link_send, bit 2 the arrival's wire_pop; 0 compiles the gate out.
+#ifndef PRISMA_LANE_LINKS
+#define PRISMA_LANE_LINKS 7
+#endif
+__device__ __forceinline__ void lane_links_bind(Sim& S) {
+    const LV& L = S.lv;
+    const uint32_t l = (uint32_t)S.lane;         // (the image's arrays hold 256 links, zero past L)
+    const bool acc = l >= (uint32_t)L.E();
+    S.lk_rinfo = S.T->rinfo[l];
+    S.lk_txd = S.T->ltx[2u * (l * 8u + T_RELAY)];
+    S.lk_txp = S.T->ltx[2u * (l * 8u + T_PFWD)];
+    S.lk_prop = S.T->ltx[2u * (l * 8u + T_RELAY) + 1u] - S.lk_txd;
+    S.lk_lim = acc ? L.acc_qmax_pkts() : L.qmax_bytes();
+    S.lk_acc = acc ? ~0u : 0u;
+    asm volatile("" : "+v"(S.lk_rinfo), "+v"(S.lk_txd), "+v"(S.lk_txp), "+v"(S.lk_prop), "+v"(S.lk_lim),
+                 "+v"(S.lk_acc));
+}
+
+// status word of link_send_lane (owner lane's, read back by the caller)
+constexpr uint32_t LST_DROP = 1u, LST_DUE = 2u, LST_RING = 4u, LST_START = 8u, LST_WIRE = 16u, LST_OLDER = 32u;
+
+// link_send in the link's lane.  The instances that run it see data and ping entries only (no
+// ctrl paths), identity overlays (rings in LDS, always stored) and the lazy completions.
+template <int FS, int LS>
+__device__ __forceinline__ int link_send_lane(const Sim& S, Regs<FS, LS>& R, Hot& H, uint32_t l, uint32_t e) {
+    const LV& L = S.lv;
+    const uint32_t dsz = L.data_size(), psz = L.ping_size();       // both readlanes first, then selects
+    const uint32_t WC = (uint32_t)L.WCAP();
+    const uint32_t size = (e & 2u) ? psz : dsz;
+    const bool me = (uint32_t)S.lane == l;
+    const uint32_t p0 = R.p0.v[0], p1 = R.p1.v[0], p2 = R.p2.v[0], qb = R.qb.v[0];
+    const uint32_t nq = p2 & 0xffffu, nw = p1 >> 16, tail = p1 & 0xffffu;
+    const uint32_t off = S.lk_rinfo & 0xffffu, cap = S.lk_rinfo >> 16;
+    // admission: queued bytes on a switch link, queued packets on an access link
+    const uint32_t have = (S.lk_acc & (nq + 1u)) | (~S.lk_acc & (qb + size));
+    const bool drop = have > S.lk_lim;
+    // an elided completion that precedes the event being executed has happened (lazy_due)
+    const uint64_t dd = ((uint64_t)(R.cp_t.v[0] - lo32(H.now)) << 32) + (uint64_t)R.cp_seq.v[0] - (uint64_t)H.cur_seq;
+    const bool due = !drop && p2 == 0x10000u && (nw == 0u || (int64_t)dd < 0);
+    const bool rfail = !drop && nw + nq + 1u > cap;
+    const bool start = !drop && !rfail && (due || (p2 >> 16) == 0u);   // :643-650
+    uint32_t st = drop ? LST_DROP : 0u;
+    st |= due ? LST_DUE : 0u;
+    st |= rfail ? LST_RING : 0u;
+    st |= start ? LST_START : 0u;
+    st |= (start && nw + 1u > WC) ? LST_WIRE : 0u;
+    st |= (start && nq != 0u) ? LST_OLDER : 0u;
+    const uint32_t s = rdl(st, l);
+    if (s & LST_DROP) return 0;
+    H.ev_launch += (s / LST_DUE) & 1u;
+    if (s & LST_RING) { fail(H, PRISMA_EBIT_RING); return 0; }
+    const uint32_t nt = (tail + 1u == cap) ? 0u : tail + 1u;
+    if (s & LST_START) {
+        const uint32_t xi = p0 >> 16;
+        uint32_t hx = e;
+        if (s & LST_OLDER) hx = S.ring[off + xi];                  // (a queue behind an idle transmitter)
+        const uint32_t nx = (xi + 1u == cap) ? 0u : xi + 1u;
+        const bool ping = (hx & 2u) != 0u;
+        const uint32_t cpt = lo32(H.now) + (ping ? S.lk_txp : S.lk_txd);
+        const uint32_t at = cpt + S.lk_prop;
+        const uint32_t cps = H.seq, as = H.seq + 1u;               // TransmitComplete, channel Receive
+        H.seq += 2u;
+        if (me) {
+            S.ring[off + tail] = e;
+            S.wt[l * WC + (xi & (WC - 1u))] = at;
+            S.wseq[l * WC + (xi & (WC - 1u))] = as;
+        }
+        R.p0.v[0] = me ? ((p0 & 0xffffu) | (nx << 16)) : p0;
+        R.p1.v[0] = me ? (nt | ((nw + 1u) << 16)) : p1;
+        R.p2.v[0] = me ? (nq | 0x10000u) : p2;
+        R.qb.v[0] = me ? qb + size - (ping ? psz : dsz) : qb;
+        R.cp_t.v[0] = me ? cpt : R.cp_t.v[0];
+        R.cp_seq.v[0] = me ? cps : R.cp_seq.v[0];
+        const bool head = me && nw == 0u;                          // the wire was empty: new head
+        R.wh_t.v[0] = head ? at : R.wh_t.v[0];
+        R.wh_seq.v[0] = head ? as : R.wh_seq.v[0];
+        if (s & LST_WIRE) fail(H, PRISMA_EBIT_WIRE);
+    } else {
+        if (me) S.ring[off + tail] = e;
+        R.p1.v[0] = me ? (nt | (nw << 16)) : p1;
+        R.p2.v[0] = me ? p2 + 1u : p2;
+        R.qb.v[0] = me ? qb + size : qb;
+    }
+    return 1;
+}
+
+// on_complete in the link's lane.  A completion is only selected while packets wait behind the
+// transmitter (select_event's cpv: busy = 1, n_queue > 0), so the dequeue and the next
+// transmission are unconditional and no field has to become uniform.
+template <int FS, int LS>
+__device__ __forceinline__ void on_complete_lane(const Sim& S, Regs<FS, LS>& R, Hot& H, uint32_t l) {
+    const LV& L = S.lv;
+    const uint32_t dsz = L.data_size(), psz = L.ping_size();
+    const uint32_t WC = (uint32_t)L.WCAP();
+    const bool me = (uint32_t)S.lane == l;
+    const uint32_t p0 = R.p0.v[0], p1 = R.p1.v[0], p2 = R.p2.v[0], qb = R.qb.v[0];
+    const uint32_t off = S.lk_rinfo & 0xffffu, cap = S.lk_rinfo >> 16;
+    const uint32_t xi = p0 >> 16, nw = p1 >> 16;
+    const uint32_t hx = S.ring[off + xi];                          // each lane its own ring's head
+    const uint32_t nx = (xi + 1u == cap) ? 0u : xi + 1u;
+    const bool ping = (hx & 2u) != 0u;
+    const uint32_t cpt = lo32(H.now) + (ping ? S.lk_txp : S.lk_txd);
+    const uint32_t at = cpt + S.lk_prop;
+    const uint32_t cps = H.seq, as = H.seq + 1u;                   // TransmitComplete, channel Receive
+    H.seq += 2u;
+    if (me) {
+        S.wt[l * WC + (xi & (WC - 1u))] = at;
+        S.wseq[l * WC + (xi & (WC - 1u))] = as;
+    }
+    R.p0.v[0] = me ? ((p0 & 0xffffu) | (nx << 16)) : p0;
+    R.p1.v[0] = me ? p1 + 0x10000u : p1;
+    R.p2.v[0] = me ? p2 - 1u : p2;                                 // busy stays 1
+    R.qb.v[0] = me ? qb - (ping ? psz : dsz) : qb;
+    R.cp_t.v[0] = me ? cpt : R.cp_t.v[0];
+    R.cp_seq.v[0] = me ? cps : R.cp_seq.v[0];
+    const bool head = me && nw == 0u;                              // the wire was empty: new head
+    R.wh_t.v[0] = head ? at : R.wh_t.v[0];
+    R.wh_seq.v[0] = head ? as : R.wh_seq.v[0];
+    if (__ballot(me && nw + 1u > WC) != 0ull) fail(H, PRISMA_EBIT_WIRE);
+}
+
 // returns 1 if enqueued, 0 if dropped (a ring overflow fails the replica)
 // link_send with the link's state already fetched (the memory-resident engine's flow event
 // issues the record load early); the register-resident engine keeps the plain form below,
@@ -868,6 +1008,9 @@ __device__ __forceinline__ int link_send_k(const Sim& S, RS& R, Hot& H, uint32_t
 template <class RS>
 __device__ __forceinline__ int link_send(const Sim& S, RS& R, Hot& H, uint32_t l, uint32_t e) {
     const LV& L = S.lv;
+    if constexpr (!RS::kMem && (PRISMA_LANE_LINKS & 2) != 0) {
+        if (S.lanel) return link_send_lane(S, R, H, l, e);
+    }
     LinkV k = link_get(R, l);
     uint32_t size = ent_size(S, e, l);
     // admission (switch links by queued bytes, access links by queued packets) as one compare
@@ -909,6 +1052,9 @@ __device__ __forceinline__ int link_send(const Sim& S, RS& R, Hot& H, uint32_t l
 template <class RS>
 __device__ __forceinline__ void on_complete(const Sim& S, RS& R, Hot& H, uint32_t l) {   // :305-336
     const LV& L = S.lv;
+    if constexpr (!RS::kMem && (PRISMA_LANE_LINKS & 1) != 0) {
+        if (S.lanel) { on_complete_lane(S, R, H, l); return; }
+    }
     if (S.mem) TP1_START();
     TP2_START();
     LinkV k = link_get(R, l);
@@ -2111,10 +2257,32 @@ __device__ __forceinline__ int mlp_action_mem(const Sim& S, uint32_t v, uint32_t
     return best;
 }
 
+// wire_pop in the link's lane (lane-resident link handlers above): every lane advances ITS head
+// and reads slot `its next head` of link l's wire -- in bounds for every lane, the owner's being
+// the slot wanted -- and the owner commits; the arrival then needs only `head` uniform
+template <int FS, int LS>
+__device__ __forceinline__ void wire_pop_lane(const Sim& S, Regs<FS, LS>& R, uint32_t l) {
+    const uint32_t WC = (uint32_t)S.lv.WCAP();
+    const bool me = (uint32_t)S.lane == l;
+    const uint32_t p0 = R.p0.v[0], p1 = R.p1.v[0];
+    const uint32_t cap = S.lk_rinfo >> 16, head = p0 & 0xffffu;
+    const uint32_t nh = (head + 1u == cap) ? 0u : head + 1u;
+    const uint32_t w = l * WC + (nh & (WC - 1u));
+    const uint32_t t = S.wt[w], s = S.wseq[w];
+    R.p0.v[0] = me ? ((p0 & 0xffff0000u) | nh) : p0;
+    R.p1.v[0] = me ? p1 - 0x10000u : p1;
+    const bool next = me && (p1 >> 16) != 1u;                       // next packet on the wire
+    R.wh_t.v[0] = next ? t : R.wh_t.v[0];
+    R.wh_seq.v[0] = next ? s : R.wh_seq.v[0];
+}
+
 // the head packet leaves the wire of link l (arrival at the far end)
 template <class RS>
 __device__ __forceinline__ void wire_pop(const Sim& S, RS& R, const Hot& H, uint32_t l, LinkV& k) {
     const LV& L = S.lv;
+    if constexpr (!RS::kMem && (PRISMA_LANE_LINKS & 4) != 0) {
+        if (S.lanel) { wire_pop_lane(S, R, l); return; }
+    }
     const uint32_t cap = ring_cap(S, l);
     k.head = (k.head + 1 == cap) ? 0 : k.head + 1;
     k.n_wire--;

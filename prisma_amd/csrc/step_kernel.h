@@ -87,6 +87,8 @@ __device__ unsigned long long g_wave_times[4 * 65536];
     sim_bind(S, lv, lds, P.topo, P.log + (size_t)r * LC.log_cap * LC.rec_bytes, LC.replica_base + (uint32_t)r, lane); \
     S.tun = TUN;                                                                                        \
     S.ctrl = CTRL;                                                                                      \
+    S.lanel = PRISMA_LANE_LINKS != 0 && (FUSED_) && (EXPL_) == 0 && LS == 1 && FS <= 4 && !TUN && !CTRL; \
+    if (S.lanel) lane_links_bind(S);                                                                    \
     if (TUN) S.ring = (uint32_t*)(P.state + (size_t)r * LC.state_bytes + LC.s_ring);   /* HBM FIFOs */  \
     uint32_t budget = (uint32_t)P.max_hops;                                                             \
     S.prio_total = StepOcc<FS, LS>::waves >= 4 ? budget : 0u;                                           \
