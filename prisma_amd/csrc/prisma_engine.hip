@@ -106,32 +106,21 @@ __global__ void __launch_bounds__(64) prisma_reset_kernel_t(KParams P) {
     }
 }
 
-// step kernels (step_kernel.h): the table-policy instances with the --train / notify_dest
-// code paths are compiled here, the in-kernel DQN-buffer ones in prisma_engine_mlp.hip, the
-// ones without those paths in prisma_engine_lite.hip / prisma_engine_lite_mlp.hip, the exploring
-// ones (prisma_run_explore) in prisma_engine_explore.hip / prisma_engine_explore_mlp.hip, the
-// reduced DQN-buffer models' in prisma_engine_lightq.hip / prisma_engine_explore_lightq.hip, the
-// ones with history-weighted exploration (prisma_run_explore_smart) in prisma_engine_smart.hip /
-// prisma_engine_smart_mlp.hip / prisma_engine_smart_lightq.hip
-const void* prisma_pick_step_lite(int fs, int ls, bool tun);
-const void* prisma_pick_step_lite_mlp(int fs, int ls, bool tun);
-const void* prisma_pick_step_fused(int fs, int ls, bool tun);
-const void* prisma_pick_step_ctrl_mlp(int fs, int ls, bool tun);
-const void* prisma_pick_step_explore(int fs, int ls, bool tun);
-const void* prisma_pick_step_explore_mlp(int fs, int ls, bool tun);
-const void* prisma_pick_step_lightq(int fs, int ls, bool tun);
-const void* prisma_pick_step_explore_lightq(int fs, int ls, bool tun);
-const void* prisma_pick_step_smart(int fs, int ls, bool tun);
-const void* prisma_pick_step_smart_mlp(int fs, int ls, bool tun);
-const void* prisma_pick_step_smart_lightq(int fs, int ls, bool tun);
-// ... and the ones with stochastic multipath routing (prisma_run_stochastic) in prisma_engine_stoch.hip
-const void* prisma_pick_step_stoch(int fs, int ls, bool tun);
-static const void* pick_step_ctrl(int fs, int ls, bool tun) { return pick_step<true, false>(fs, ls, tun); }
+// step kernels: this unit compiles the table-policy set with the --train / notify_dest code paths;
+// the other sets and their translation units are listed in step_kernel.h (PRISMA_STEP_SETS)
+PRISMA_TU_STEP_SET(kSetCtrl)
+const void* prisma_pick_step(StepSet set, int fs, int ls, bool tun) {
+    switch (set) {
+#define PK(ID_, ...) case kSet##ID_: return prisma_pick_step_set<kSet##ID_>(fs, ls, tun);
+    PRISMA_STEP_SETS(PK)
+#undef PK
+    default: return nullptr;
+    }
+}
 
-template <int FS, int LS> const void* reset_kernel() { return (const void*)prisma_reset_kernel_t<FS, LS>; }
 static const void* pick_reset(int fs, int ls) {
-#define PK(F_, L_) if (fs == F_ && ls == L_) return reset_kernel<F_, L_>();
-    PK(1, 1) PK(1, 2) PK(1, 4) PK(2, 1) PK(2, 2) PK(2, 4) PK(4, 1) PK(4, 2) PK(4, 4) PK(8, 1) PK(8, 2) PK(8, 4)
+#define PK(F_, L_) if (fs == F_ && ls == L_) return (const void*)prisma_reset_kernel_t<F_, L_>;
+    PRISMA_STEP_SHAPES(PK)
 #undef PK
     return nullptr;
 }
@@ -332,18 +321,11 @@ struct prisma_env {
     unsigned char* d_log = nullptr;
     prisma_counters_t* d_cnt = nullptr;
     Layout* d_lay = nullptr;
-    const void* k_step = nullptr;
-    const void* k_step_mlp = nullptr;
-    const void* k_fused = nullptr;       // fused-only table instance (run_fused), or null: k_step runs tables too
-    const void* k_reset = nullptr;
-    const void* k_explore = nullptr;     // exploring instances (prisma_run_explore): register engine
-    const void* k_explore_mlp = nullptr; // without the ctrl paths only
-    const void* k_lightq = nullptr;      // reduced DQN-buffer models (PRISMA_POLICY_DQN_LITE ...): register
-    const void* k_explore_lightq = nullptr; // engine without the ctrl paths only
-    const void* k_smart = nullptr;       // history-weighted exploration (prisma_run_explore_smart): register
-    const void* k_smart_mlp = nullptr;   // engine without the ctrl paths only
-    const void* k_smart_lightq = nullptr;
-    const void* k_stoch = nullptr;       // stochastic multipath routing (prisma_run_stochastic): likewise
+    // launch slots by instance set (step_kernel.h kStepSets): the kernel for this env's shape and
+    // its dynamic LDS, or null where the env has no instance of the set (prisma_create).  The
+    // memory-resident engine's two step kernels sit in the table and DQN-buffer slots.
+    struct StepSlot { const void* kernel = nullptr; uint32_t lds_bytes = 0; } step[kNumStepSets];
+    StepSlot reset;
     std::vector<int32_t> ovrow;          // [N + 1] overlay CSR rows by underlay id (prisma_action_history_layout)
     float* d_lq_rp = nullptr;            // their interleaved weights (sized for the largest, DQN_LITE)
     float* d_mlp_rp = nullptr;           // interleaved DQN-buffer layers 2-4 (prisma_run, mode 4)
@@ -1045,6 +1027,20 @@ static int build_layout(const prisma_topology_t* T, const prisma_params_t* P, La
     return PRISMA_OK;
 }
 
+// Does the env run the step kernels with the ctrl paths?  The --train echo and notify_dest paths
+// (and the ns-3 streams: flow_next) are compiled only into the instances that need them; the
+// tunnelled-overlay instances without them carry an 18-bit decision index in relay entries
+// (engine_layout.h rip_make).  Their wrap check (a relay entry older than the log,
+// PRISMA_EBIT_LOGWRAP) needs log ages up to log_cap to stay below 2^18, so a log of 2^18 records or
+// more takes the others (22-bit index).  (The memory-resident engine runs identity overlays only.)
+static bool ctrl_env(const Layout& L) {
+    return L.train || L.notify_dest || L.rng_mode || (L.tunnels && L.log_cap >= (1u << kRipDecBits));
+}
+// the general table set (prisma_step, and tables where there is no fused-only instance) and the
+// DQN-buffer set of an env
+static StepSet table_set(bool ctrl) { return ctrl ? kSetCtrl : kSetLite; }
+static StepSet mlp_set(bool ctrl) { return ctrl ? kSetCtrlMlp : kSetLiteMlp; }
+
 extern "C" int prisma_create(const prisma_topology_t* topo, const prisma_params_t* params, int32_t n_replicas,
                              int32_t device, prisma_env_t** out) {
     if (!topo || !params || !out || n_replicas < 1) return set_err(PRISMA_ERR_ARG, "null argument or n_replicas < 1");
@@ -1131,62 +1127,32 @@ extern "C" int prisma_create(const prisma_topology_t* topo, const prisma_params_
         prisma_destroy(e);
         return set_err(PRISMA_ERR_DEVICE, "device initialisation failed");
     }
-    if (L.mem) {
-        const bool ctrl = L.train || L.notify_dest || L.rng_mode;   // (ns-3 streams: CTRL instances, flow_next)
-        e->k_step = prisma_mem_kernel(0, ctrl);
-        e->k_reset = prisma_mem_kernel(1, ctrl);
-        e->k_step_mlp = prisma_mem_kernel(2, ctrl);
-    } else {
-        // the --train echo and notify_dest paths (and the ns-3 streams) are compiled only into the
-        // instances that need them; the tunnelled-overlay instances without them carry an 18-bit
-        // decision index in relay entries (engine_layout.h rip_make).  Their wrap check (a relay
-        // entry older than the log, PRISMA_EBIT_LOGWRAP) needs log ages up to log_cap to stay below
-        // 2^18, so a log of 2^18 records or more takes the others (22-bit index)
-        const bool ctrl = L.train || L.notify_dest || L.rng_mode || (L.tunnels && L.log_cap >= (1u << kRipDecBits));
-        auto pick = ctrl ? pick_step_ctrl : prisma_pick_step_lite;
-        auto pick_mlp = ctrl ? prisma_pick_step_ctrl_mlp : prisma_pick_step_lite_mlp;
-        e->k_step = pick(L.FS, L.LS, L.tunnels != 0u);
-        e->k_reset = pick_reset(L.FS, L.LS);
-        e->k_step_mlp = pick_mlp(L.FS, L.LS, L.tunnels != 0u);
-        // fused table runs have instances of their own (step_kernel.h FUSED) where the env is an
-        // identity overlay without the ctrl paths and its table sits in LDS (the picker has none
-        // for tunnelled overlays); elsewhere k_step serves them as well
-        if (!ctrl && L.table_in_lds) e->k_fused = prisma_pick_step_fused(L.FS, L.LS, L.tunnels != 0u);
-        if (!ctrl) {
-            e->k_explore = prisma_pick_step_explore(L.FS, L.LS, L.tunnels != 0u);
-            e->k_explore_mlp = prisma_pick_step_explore_mlp(L.FS, L.LS, L.tunnels != 0u);
-            e->k_lightq = prisma_pick_step_lightq(L.FS, L.LS, L.tunnels != 0u);
-            e->k_explore_lightq = prisma_pick_step_explore_lightq(L.FS, L.LS, L.tunnels != 0u);
-            e->k_smart = prisma_pick_step_smart(L.FS, L.LS, L.tunnels != 0u);
-            e->k_smart_mlp = prisma_pick_step_smart_mlp(L.FS, L.LS, L.tunnels != 0u);
-            e->k_smart_lightq = prisma_pick_step_smart_lightq(L.FS, L.LS, L.tunnels != 0u);
-            e->k_stoch = prisma_pick_step_stoch(L.FS, L.LS, L.tunnels != 0u);
-        }
-        e->kinfo.ctrl = ctrl ? 1u : 0u;
-        e->kinfo.relay_ip = (L.tunnels && !ctrl) ? 1u : 0u;
-        e->kinfo.relay_dec_bits = L.tunnels ? (ctrl ? 22u : kRipDecBits) : 0u;
+    const bool ctrl = ctrl_env(L), tun = L.tunnels != 0u;
+    e->reset.kernel = L.mem ? prisma_mem_kernel(1, ctrl) : pick_reset(L.FS, L.LS);
+    e->reset.lds_bytes = L.lds_bytes;
+    (void)hipFuncSetAttribute(e->reset.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bytes);
+    for (int s = 0; s < kNumStepSets; ++s) {
+        const StepSetInfo& I = kStepSets[s];
+        prisma_env::StepSlot& slot = e->step[s];
+        slot.lds_bytes = I.mlp ? L.lds_mlp_bytes : L.lds_bytes;
+        // an env's sets are the ones with its ctrl paths or the ones without.  The fused-only table
+        // set serves identity overlays whose table sits in LDS (the picker has none for tunnelled
+        // overlays); elsewhere the general table slot runs fused tables as well (run_slot).  The
+        // memory-resident engine has its two greedy kernels only.
+        if (I.ctrl != ctrl || (s == kSetFused && !L.table_in_lds)) continue;
+        if (!L.mem) slot.kernel = prisma_pick_step((StepSet)s, L.FS, L.LS, tun);
+        else if (s == table_set(ctrl) || s == mlp_set(ctrl)) slot.kernel = prisma_mem_kernel(I.mlp ? 2 : 0, ctrl);
+        if (slot.kernel)
+            (void)hipFuncSetAttribute(slot.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)slot.lds_bytes);
     }
     e->kinfo.engine = L.mem ? PRISMA_ENGINE_MEMORY : PRISMA_ENGINE_REGISTER;
     e->kinfo.flow_slots = L.mem ? 0 : L.FS;
     e->kinfo.link_slots = L.mem ? 0 : L.LS;
-    e->kinfo.tunnels = L.tunnels ? 1u : 0u;
-    if (L.mem) e->kinfo.ctrl = (L.train || L.notify_dest || L.rng_mode) ? 1u : 0u;
-    (void)hipFuncSetAttribute(e->k_step_mlp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_mlp_bytes);
-    (void)hipFuncSetAttribute(e->k_step, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bytes);
-    (void)hipFuncSetAttribute(e->k_reset, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bytes);
-    if (e->k_fused) (void)hipFuncSetAttribute(e->k_fused, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bytes);
-    if (e->k_explore) (void)hipFuncSetAttribute(e->k_explore, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bytes);
-    if (e->k_explore_mlp)
-        (void)hipFuncSetAttribute(e->k_explore_mlp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_mlp_bytes);
-    if (e->k_lightq) (void)hipFuncSetAttribute(e->k_lightq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_mlp_bytes);
-    if (e->k_explore_lightq)
-        (void)hipFuncSetAttribute(e->k_explore_lightq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_mlp_bytes);
-    if (e->k_smart) (void)hipFuncSetAttribute(e->k_smart, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bytes);
-    if (e->k_smart_mlp)
-        (void)hipFuncSetAttribute(e->k_smart_mlp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_mlp_bytes);
-    if (e->k_smart_lightq)
-        (void)hipFuncSetAttribute(e->k_smart_lightq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_mlp_bytes);
-    if (e->k_stoch) (void)hipFuncSetAttribute(e->k_stoch, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bytes);
+    e->kinfo.tunnels = tun ? 1u : 0u;
+    e->kinfo.ctrl = ctrl ? 1u : 0u;
+    // (tunnelled overlays without the ctrl paths: an 18-bit decision index in relay entries)
+    e->kinfo.relay_ip = (tun && !ctrl) ? 1u : 0u;
+    e->kinfo.relay_dec_bits = tun ? (ctrl ? 22u : kRipDecBits) : 0u;
     *out = e;
     return PRISMA_OK;
 }
@@ -1205,15 +1171,42 @@ static KParams base_params(prisma_env_t* e) {
     return P;
 }
 
-static int launch(prisma_env_t* e, const void* kern, KParams P, void* stream) {
+static int launch(prisma_env_t* e, const prisma_env::StepSlot& slot, KParams P, void* stream) {
     (void)hipSetDevice(e->device);
     void* args[] = { &P };
-    const bool mlp_kern = kern == e->k_step_mlp || kern == e->k_explore_mlp || kern == e->k_lightq ||
-                          kern == e->k_explore_lightq || kern == e->k_smart_mlp || kern == e->k_smart_lightq;
-    const size_t lds = mlp_kern ? e->lay.lds_mlp_bytes : e->lay.lds_bytes;
-    hipError_t err = hipLaunchKernel(kern, dim3((unsigned)e->R), dim3(kWave), args, lds, (hipStream_t)stream);
+    hipError_t err = hipLaunchKernel(slot.kernel, dim3((unsigned)e->R), dim3(kWave), args, slot.lds_bytes,
+                                     (hipStream_t)stream);
     if (err == hipSuccess) err = hipGetLastError();
     if (err != hipSuccess) return set_err(PRISMA_ERR_LAUNCH, std::string("kernel launch failed: ") + hipGetErrorString(err));
+    return PRISMA_OK;
+}
+
+// The slot of a fused run, by its exploration family (kStepSets' expl: 0 greedy, 1 epsilon-greedy,
+// 2 history-weighted, 3 stochastic routing) and model (0 table, 1 DQN-buffer, 2 reduced DQN-buffer).
+// Greedy tables run on the fused-only instance where the env has one, else on the general one.
+static const prisma_env::StepSlot& run_slot(const prisma_env_t* e, int expl, int model) {
+    const bool ctrl = e->kinfo.ctrl != 0u;
+    const StepSet sets[4][3] = {
+        { e->step[kSetFused].kernel ? kSetFused : table_set(ctrl), mlp_set(ctrl), kSetLightq },
+        { kSetExplore, kSetExploreMlp, kSetExploreLightq },
+        { kSetSmart, kSetSmartMlp, kSetSmartLightq },
+        { kSetStoch, kSetStoch, kSetStoch } };           // (no model: prisma_run_stochastic's table)
+    return e->step[sets[expl][model]];
+}
+
+// The refusal of a run on an env without the instance sets it needs: they exist for the
+// register-resident engine without the ctrl paths only.  who: the entry point (or the policies),
+// what: the instances, both in the message's words.
+static int refuse_without(const prisma_env_t* e, const char* who, const char* what,
+                          std::initializer_list<StepSet> sets) {
+    if (e->lay.mem)
+        return set_err(PRISMA_ERR_CONFIG, std::string(who) + ": the memory-resident engine has no " + what);
+    bool have = !e->kinfo.ctrl;
+    for (StepSet s : sets) have = have && e->step[s].kernel;
+    if (!have)
+        return set_err(PRISMA_ERR_CONFIG, std::string(who) + ": this env runs the step kernels with the ctrl paths (train, "
+                                          "notify_dest, ns-3 streams, or a tunnelled overlay with log_capacity >= 2^18), "
+                                          "which have no " + what);
     return PRISMA_OK;
 }
 
@@ -1222,7 +1215,7 @@ static int auto_reset(prisma_env_t* e, void* stream) {
     if (!e->lay.auto_reset) return PRISMA_OK;
     KParams P = base_params(e);
     P.mode = 3;
-    return launch(e, e->k_reset, P, stream);
+    return launch(e, e->reset, P, stream);
 }
 
 extern "C" int prisma_reset(prisma_env_t* e, uint32_t episode, void* stream) {
@@ -1230,7 +1223,7 @@ extern "C" int prisma_reset(prisma_env_t* e, uint32_t episode, void* stream) {
     KParams P = base_params(e);
     P.mode = 0;
     P.episode = episode;
-    int rc = launch(e, e->k_reset, P, stream);
+    int rc = launch(e, e->reset, P, stream);
     if (!rc) e->reset_done = true;
     return rc;
 }
@@ -1246,7 +1239,7 @@ extern "C" int prisma_step(prisma_env_t* e, const int32_t* actions, int32_t* obs
     P.mask_out = mask_out;
     P.node_out = node_out;
     P.max_hops = 0x7fffffff;
-    int rc = launch(e, e->k_step, P, stream);
+    int rc = launch(e, e->step[table_set(e->kinfo.ctrl != 0u)], P, stream);
     return rc ? rc : auto_reset(e, stream);
 }
 
@@ -1259,65 +1252,47 @@ static int run_fused(prisma_env_t* e, int32_t policy, const void* policy_data, i
                                        "of PRISMA_POLICY_DQN_LITE ... _DQN_LIGHTER_3 (fp32 weights), with device data");
     if (max_hops < 1) return set_err(PRISMA_ERR_ARG, "max_hops must be >= 1");
     const bool lightq = policy >= PRISMA_POLICY_DQN_LITE;
-    if (lightq) {
-        // the reduced models are compiled into instances of their own, which exist for the
-        // register-resident engine without the ctrl paths only (as the exploring ones)
-        if (e->lay.mem)
-            return set_err(PRISMA_ERR_CONFIG, "PRISMA_POLICY_DQN_LITE ... _DQN_LIGHTER_3: the memory-resident engine has no "
-                                              "instances with the reduced DQN-buffer models");
-        if (e->kinfo.ctrl || !e->k_lightq || !e->k_explore_lightq)
-            return set_err(PRISMA_ERR_CONFIG, "PRISMA_POLICY_DQN_LITE ... _DQN_LIGHTER_3: this env runs the step kernels with "
-                                              "the ctrl paths (train, notify_dest, ns-3 streams, or a tunnelled overlay "
-                                              "with log_capacity >= 2^18), which have no instances with the reduced "
-                                              "DQN-buffer models");
-    }
+    // the reduced models are compiled into instances of their own (as the exploring ones)
+    if (lightq)
+        if (int rc = refuse_without(e, "PRISMA_POLICY_DQN_LITE ... _DQN_LIGHTER_3",
+                                    "instances with the reduced DQN-buffer models", { kSetLightq, kSetExploreLightq }))
+            return rc;
     KParams P = base_params(e);
     if (policy == PRISMA_POLICY_TABLE) {
         P.mode = 2;
         P.table = (const uint8_t*)policy_data;
-    } else if (lightq) {
+    } else {
         // widths (B, H, NH) of include/prisma.h's table: models.py:184-227, 39-85, 87-133, 135-181
         static const int kDims[4][3] = { {16, 32, 2}, {16, 32, 1}, {8, 16, 1}, {4, 8, 1} };
-        const int* dm = kDims[policy - PRISMA_POLICY_DQN_LITE];
+        const int* dm = kDims[lightq ? policy - PRISMA_POLICY_DQN_LITE : 0];
         P.mode = 4;
         P.mlp = (const float*)policy_data;
-        P.lq_dims = lq_pack_dims(dm[0], dm[1], dm[2]);
-        // re-interleaved every call on the caller's stream, as the DQN-buffer weights below
+        if (lightq) P.lq_dims = lq_pack_dims(dm[0], dm[1], dm[2]);
+        // the weights may change between calls (training): re-interleave them every call, on the
+        // caller's stream ahead of the step kernel (~1 us at GEANT size).  The reduced models share
+        // one buffer, sized for the largest (DQN_LITE, kDims[0]).
         const int N = e->lay.N, D = e->lay.max_deg;
+        float*& rp = lightq ? e->d_lq_rp : e->d_mlp_rp;
+        const size_t cap = (size_t)N * (lightq ? lq_rp_node_floats(D, 16, 32, 2) : mlp_rp_node_floats(D));
+        const size_t n = lightq ? (size_t)N * lq_rp_node_floats(D, dm[0], dm[1], dm[2]) : cap;
         (void)hipSetDevice(e->device);
-        if (!e->d_lq_rp &&
-            !HIP_OK(hipMalloc(&e->d_lq_rp, (size_t)N * lq_rp_node_floats(D, 16, 32, 2) * sizeof(float))))
-            return set_err(PRISMA_ERR_NOMEM, "hipMalloc of the interleaved reduced-model weights failed");
-        const size_t n = (size_t)N * lq_rp_node_floats(D, dm[0], dm[1], dm[2]);
+        if (!rp && !HIP_OK(hipMalloc(&rp, cap * sizeof(float))))
+            return set_err(PRISMA_ERR_NOMEM, lightq ? "hipMalloc of the interleaved reduced-model weights failed"
+                                                    : "hipMalloc of the interleaved DQN-buffer weights failed");
         const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 4096);
-        hipLaunchKernelGGL(prisma_lightq_repack_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
-                           P.mlp, e->d_lq_rp, N, D, dm[0], dm[1], dm[2]);
+        if (lightq)
+            hipLaunchKernelGGL(prisma_lightq_repack_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
+                               P.mlp, rp, N, D, dm[0], dm[1], dm[2]);
+        else
+            hipLaunchKernelGGL(prisma_mlp_repack_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
+                               P.mlp, rp, N, D);
         if (!HIP_OK(hipGetLastError())) return set_err(PRISMA_ERR_LAUNCH, "repack kernel launch failed");
-        P.mlp_rp = e->d_lq_rp;
-    } else {
-        P.mode = 4;
-        P.mlp = (const float*)policy_data;
-        // the weights may change between calls (training): re-interleave them every call,
-        // on the caller's stream ahead of the step kernel (~1 us at GEANT size)
-        const int N = e->lay.N, D = e->lay.max_deg;
-        const size_t n = (size_t)N * mlp_rp_node_floats(D);
-        (void)hipSetDevice(e->device);
-        if (!e->d_mlp_rp && !HIP_OK(hipMalloc(&e->d_mlp_rp, n * sizeof(float))))
-            return set_err(PRISMA_ERR_NOMEM, "hipMalloc of the interleaved DQN-buffer weights failed");
-        const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 4096);
-        hipLaunchKernelGGL(prisma_mlp_repack_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
-                           P.mlp, e->d_mlp_rp, N, D);
-        if (!HIP_OK(hipGetLastError())) return set_err(PRISMA_ERR_LAUNCH, "repack kernel launch failed");
-        P.mlp_rp = e->d_mlp_rp;
+        P.mlp_rp = rp;
     }
     P.max_hops = max_hops;
     P.explore_thr = explore_thr;
     P.action_hist = action_hist;
-    const void* kern = action_hist ? (lightq ? e->k_smart_lightq : P.mode == 4 ? e->k_smart_mlp : e->k_smart)
-                     : lightq ? (explore_thr ? e->k_explore_lightq : e->k_lightq)
-                     : explore_thr ? (P.mode == 4 ? e->k_explore_mlp : e->k_explore)
-                                   : (P.mode == 4 ? e->k_step_mlp : e->k_fused ? e->k_fused : e->k_step);
-    int rc = launch(e, kern, P, stream);
+    int rc = launch(e, run_slot(e, action_hist ? 2 : explore_thr ? 1 : 0, lightq ? 2 : P.mode == 4 ? 1 : 0), P, stream);
     // with auto_reset (register engine) the step kernel already continued every replica whose
     // episode ended into the next one; this launch refreshes the spare images it used, and
     // starts the next episode of the replicas it could not continue (memory engine; a second
@@ -1334,14 +1309,9 @@ extern "C" int prisma_run_explore(prisma_env_t* e, int32_t policy, const void* p
                                   const uint32_t* explore_thr, void* stream) {
     if (!e) return set_err(PRISMA_ERR_ARG, "null env");
     if (!explore_thr) return set_err(PRISMA_ERR_ARG, "explore_thr must be a device uint32 [n_nodes] array");
-    // exploration is compiled into instances of its own, which exist for the register-resident
-    // engine without the ctrl paths only
-    if (e->lay.mem)
-        return set_err(PRISMA_ERR_CONFIG, "prisma_run_explore: the memory-resident engine has no exploring instances");
-    if (e->kinfo.ctrl || !e->k_explore || !e->k_explore_mlp)
-        return set_err(PRISMA_ERR_CONFIG, "prisma_run_explore: this env runs the step kernels with the ctrl paths (train, "
-                                          "notify_dest, ns-3 streams, or a tunnelled overlay with log_capacity >= 2^18), "
-                                          "which have no exploring instances");
+    // exploration is compiled into instances of its own
+    if (int rc = refuse_without(e, "prisma_run_explore", "exploring instances", { kSetExplore, kSetExploreMlp }))
+        return rc;
     return run_fused(e, policy, policy_data, max_hops, explore_thr, nullptr, stream);
 }
 
@@ -1357,13 +1327,8 @@ extern "C" int prisma_run_explore_smart(prisma_env_t* e, int32_t policy, const v
                                         void* stream) {
     if (!e) return set_err(PRISMA_ERR_ARG, "null env");
     if (!explore_thr) return set_err(PRISMA_ERR_ARG, "explore_thr must be a device uint32 [n_nodes] array");
-    // as the exploring instances: the register-resident engine without the ctrl paths only
-    if (e->lay.mem)
-        return set_err(PRISMA_ERR_CONFIG, "prisma_run_explore_smart: the memory-resident engine has no exploring instances");
-    if (e->kinfo.ctrl || !e->k_smart || !e->k_smart_mlp || !e->k_smart_lightq)
-        return set_err(PRISMA_ERR_CONFIG, "prisma_run_explore_smart: this env runs the step kernels with the ctrl paths "
-                                          "(train, notify_dest, ns-3 streams, or a tunnelled overlay with log_capacity "
-                                          ">= 2^18), which have no exploring instances");
+    if (int rc = refuse_without(e, "prisma_run_explore_smart", "exploring instances",
+                                { kSetSmart, kSetSmartMlp, kSetSmartLightq })) return rc;
     if (!action_hist || hist_words != (uint64_t)e->R * (uint64_t)e->ovrow.back())
         return set_err(PRISMA_ERR_ARG, "prisma_run_explore_smart: action_hist must be a device uint32 [n_replicas][T] "
                                        "array and hist_words = n_replicas * T (prisma_action_history_layout)");
@@ -1373,14 +1338,8 @@ extern "C" int prisma_run_explore_smart(prisma_env_t* e, int32_t policy, const v
 extern "C" int prisma_run_stochastic(prisma_env_t* e, const uint32_t* tab, uint64_t tab_words, int32_t max_hops,
                                      void* stream) {
     if (!e) return set_err(PRISMA_ERR_ARG, "null env");
-    // as the exploring instances: the register-resident engine without the ctrl paths only
-    if (e->lay.mem)
-        return set_err(PRISMA_ERR_CONFIG, "prisma_run_stochastic: the memory-resident engine has no instances with "
-                                          "stochastic routing");
-    if (e->kinfo.ctrl || !e->k_stoch)
-        return set_err(PRISMA_ERR_CONFIG, "prisma_run_stochastic: this env runs the step kernels with the ctrl paths "
-                                          "(train, notify_dest, ns-3 streams, or a tunnelled overlay with log_capacity "
-                                          ">= 2^18), which have no instances with stochastic routing");
+    if (int rc = refuse_without(e, "prisma_run_stochastic", "instances with stochastic routing", { kSetStoch }))
+        return rc;
     const uint64_t NO = (uint64_t)e->lay.NO;
     if (!tab || tab_words != NO * NO * (uint64_t)e->ovrow.back())
         return set_err(PRISMA_ERR_ARG, "prisma_run_stochastic: tab must be a device uint32 [NO][NO][T] array and "
@@ -1391,7 +1350,7 @@ extern "C" int prisma_run_stochastic(prisma_env_t* e, const uint32_t* tab, uint6
     P.mode = 2;                          // a fused run: the episode restart and the hop budget as prisma_run's
     P.max_hops = max_hops;
     P.stoch_tab = tab;
-    int rc = launch(e, e->k_stoch, P, stream);
+    int rc = launch(e, run_slot(e, 3, 0), P, stream);
     return rc ? rc : auto_reset(e, stream);
 }
 

@@ -3,6 +3,6 @@
 // notify_dest code paths (step_kernel.h): prisma_run_explore with PRISMA_POLICY_TABLE.
 #include "step_kernel.h"
 
-const void* prisma_pick_step_explore(int fs, int ls, bool tun) { return pick_step<false, false, true>(fs, ls, tun); }
+PRISMA_TU_STEP_SET(kSetExplore)
 
 PRISMA_TU_TIMING(prisma_debug_timing_explore)

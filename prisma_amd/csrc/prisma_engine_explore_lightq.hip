@@ -4,6 +4,6 @@
 // (step_kernel.h): prisma_run_explore with PRISMA_POLICY_DQN_LITE ... _DQN_LIGHTER_3.
 #include "step_kernel.h"
 
-const void* prisma_pick_step_explore_lightq(int fs, int ls, bool tun) { return pick_step<false, true, true, true>(fs, ls, tun); }
+PRISMA_TU_STEP_SET(kSetExploreLightq)
 
 PRISMA_TU_TIMING(prisma_debug_timing_explore_lightq)

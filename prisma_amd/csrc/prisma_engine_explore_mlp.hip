@@ -4,6 +4,6 @@
 // PRISMA_POLICY_DQN_BUFFER.
 #include "step_kernel.h"
 
-const void* prisma_pick_step_explore_mlp(int fs, int ls, bool tun) { return pick_step<false, true, true>(fs, ls, tun); }
+PRISMA_TU_STEP_SET(kSetExploreMlp)
 
 PRISMA_TU_TIMING(prisma_debug_timing_explore_mlp)

@@ -5,7 +5,7 @@
 // them); prisma_step and every other env launch the general instances.
 #include "step_kernel.h"
 
-const void* prisma_pick_step_fused(int fs, int ls, bool tun) { return pick_step_fused<false>(fs, ls, tun); }
+PRISMA_TU_STEP_SET(kSetFused)
 
 PRISMA_TU_TIMING(prisma_debug_timing_fused)
 PRISMA_TU_WAVE_TIMES(prisma_debug_wave_times_fused)

@@ -4,6 +4,6 @@
 // code paths (step_kernel.h): prisma_run with PRISMA_POLICY_DQN_LITE ... _DQN_LIGHTER_3.
 #include "step_kernel.h"
 
-const void* prisma_pick_step_lightq(int fs, int ls, bool tun) { return pick_step<false, true, false, true>(fs, ls, tun); }
+PRISMA_TU_STEP_SET(kSetLightq)
 
 PRISMA_TU_TIMING(prisma_debug_timing_lightq)

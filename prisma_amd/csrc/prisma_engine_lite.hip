@@ -3,7 +3,7 @@
 // neither is set (every table-policy benchmark configuration, the headline among them).
 #include "step_kernel.h"
 
-const void* prisma_pick_step_lite(int fs, int ls, bool tun) { return pick_step<false, false>(fs, ls, tun); }
+PRISMA_TU_STEP_SET(kSetLite)
 
 PRISMA_TU_TIMING(prisma_debug_timing_lite)
 PRISMA_TU_WAVE_TIMES(prisma_debug_wave_times_lite)

@@ -3,6 +3,6 @@
 // configs 3 and 4.
 #include "step_kernel.h"
 
-const void* prisma_pick_step_lite_mlp(int fs, int ls, bool tun) { return pick_step<false, true>(fs, ls, tun); }
+PRISMA_TU_STEP_SET(kSetLiteMlp)
 
 PRISMA_TU_TIMING(prisma_debug_timing_lite_mlp)

@@ -3,6 +3,6 @@
 // and notify_dest code paths (step_kernel.h): prisma_run_explore_smart with PRISMA_POLICY_TABLE.
 #include "step_kernel.h"
 
-const void* prisma_pick_step_smart(int fs, int ls, bool tun) { return pick_step_smart<false>(fs, ls, tun); }
+PRISMA_TU_STEP_SET(kSetSmart)
 
 PRISMA_TU_TIMING(prisma_debug_timing_smart)

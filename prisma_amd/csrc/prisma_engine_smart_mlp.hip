@@ -4,6 +4,6 @@
 // with PRISMA_POLICY_DQN_BUFFER.
 #include "step_kernel.h"
 
-const void* prisma_pick_step_smart_mlp(int fs, int ls, bool tun) { return pick_step_smart<true>(fs, ls, tun); }
+PRISMA_TU_STEP_SET(kSetSmartMlp)
 
 PRISMA_TU_TIMING(prisma_debug_timing_smart_mlp)

@@ -3,6 +3,6 @@
 // --train echo and notify_dest code paths (step_kernel.h): prisma_run_stochastic.
 #include "step_kernel.h"
 
-const void* prisma_pick_step_stoch(int fs, int ls, bool tun) { return pick_step_stoch<false>(fs, ls, tun); }
+PRISMA_TU_STEP_SET(kSetStoch)
 
 PRISMA_TU_TIMING(prisma_debug_timing_stoch)

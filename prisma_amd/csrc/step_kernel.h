@@ -1,8 +1,5 @@
-// step_kernel.h -- the register-resident engine's step kernel template and its instance table,
-// included by prisma_engine.hip (instances with the --train echo / notify_dest code, CTRL) and
-// prisma_engine_lite.hip (instances without it: the compiler allocates registers for every
-// path a kernel contains, and these rarely-taken ones cost the common case ~2 %), and by
-// prisma_engine_fused.hip (table instances for fused runs only, without the external-policy path).
+// step_kernel.h -- the register-resident engine's step kernel templates and the table of their
+// instance sets (StepSet, kStepSets), included by every translation unit that compiles one set.
 #pragma once
 #include "engine_core.h"
 
@@ -16,24 +13,63 @@ template <int FS, int LS> struct StepOcc {
     static constexpr int mlp_batch = waves >= 4 ? 4 : 8;
 };
 
-// MLP: the in-kernel DQN-buffer policy is compiled in (mode 4 only); the table /
-// external instances carry none of its code or registers.  CTRL: the --train echo and
-// notify_dest paths are compiled in (used when either is set).  EXPL: epsilon-greedy exploration
-// of the fused policy (engine_core.h explore_action) -- instances of their own, so the greedy
-// ones keep their code and registers.  (The parameter sits in the kernel itself: with the body in
-// a shared inlined function taking the arguments by reference the headline instance came out
-// with 7 more SGPR spill slots and the DQN-buffer one with 16 B more scratch.)  LQ: the MLP is the
-// reduced DQN-buffer models' decision (engine_core.h lightq_action_reg; widths in KParams::lq_dims)
-// -- instance sets of their own again, greedy and exploring, without the ctrl paths.  FUSED: the
-// table instances that only fused runs (prisma_run with a table) launch, for identity-overlay envs
-// without the ctrl paths whose table sits in LDS: event_loop's table_mode and the table's place are compile-time
-// constants there, so the external-policy exit of an arrival (the Decision stored to the header,
-// the pending observation, the PENDING record), the P.actions branch and the HBM table pointer are
-// not in the kernel.  The MLP / LQ instances fold table_mode already (MLP is a template argument);
-// the general table instances keep the run-time value and serve prisma_step, the ctrl envs, envs
-// whose table stays in HBM and the tunnelled overlays (A/B, profiles/fused_inst/: headline +3.2 %,
-// SP at its shape +2.6 %, but config 3's SP line on the tunnelled (2, 1) instance -0.35 % at a
-// 0.25 % spread, so those are not instantiated).
+// The instance sets: one translation unit each (prisma_engine_<name>.hip; ctrl in prisma_engine.hip,
+// ctrl_mlp in prisma_engine_mlp.hip), so the sets compile in parallel.  This table is the list of
+// sets: a row gives the template arguments of the set's kernels (step_kernel below), and prisma_create
+// fills one launch slot per row from it (which also says what adding a set touches).
+//   mlp:   the in-kernel model is compiled in (mode 4 only) and its LDS is part of the launch
+//          (Layout::lds_mlp_bytes, else lds_bytes); the table / external instances carry none of
+//          its code or registers.
+//   ctrl:  the --train echo and notify_dest paths are compiled in; these sets serve the envs that
+//          need them (ns-3 streams and tunnelled overlays with a log of 2^18 records too), the
+//          others every other env.
+//   expl:  event_loop's EXPL -- 0 greedy, 1 epsilon-greedy exploration of the fused policy
+//          (engine_core.h explore_action), 2 history-weighted exploration (smart_explore_action),
+//          3 stochastic multipath routing (stoch_action).  Sets of their own, so the greedy ones keep
+//          their code and registers.  (The parameter sits in the kernel itself: with the body in a
+//          shared inlined function taking the arguments by reference the headline instance came out
+//          with 7 more SGPR spill slots and the DQN-buffer one with 16 B more scratch.)
+//   lq:    the model is one of the reduced DQN-buffer models (lightq_action_reg; widths in
+//          KParams::lq_dims).
+//   fused: the table instances that only fused runs (prisma_run with a table) launch, on
+//          identity-overlay envs whose table sits in LDS: event_loop's table_mode and the table's
+//          place are compile-time constants there, so the external-policy exit of an arrival (the
+//          Decision stored to the header, the pending observation, the PENDING record), the
+//          P.actions branch and the HBM table pointer are not in the kernel.  The mlp / lq sets
+//          fold table_mode already; the general table sets keep the run-time value and serve
+//          prisma_step, the ctrl envs, envs whose table stays in HBM and the tunnelled overlays
+//          (A/B, profiles/fused_inst/: headline +3.2 %, SP at its shape +2.6 %, but config 3's SP
+//          line on the tunnelled (2, 1) instance -0.35 % at a 0.25 % spread, so those are not
+//          instantiated).  (stoch: event_loop's folding only -- no table is read and no external
+//          action taken, so it holds for the tunnelled ones as well.)
+#define PRISMA_STEP_SETS(X)                                                                             \
+    /* id            name              mlp    ctrl   expl lq     fused */                               \
+    X(Ctrl,          "ctrl",           false, true,  0,   false, false) /* prisma_step, table runs: ctrl envs */ \
+    X(CtrlMlp,       "ctrl_mlp",       true,  true,  0,   false, false) /* PRISMA_POLICY_DQN_BUFFER: ctrl envs */ \
+    X(Lite,          "lite",           false, false, 0,   false, false) /* prisma_step, table runs: other envs */ \
+    X(LiteMlp,       "lite_mlp",       true,  false, 0,   false, false) /* PRISMA_POLICY_DQN_BUFFER (configs 3, 4) */ \
+    X(Fused,         "fused",          false, false, 0,   false, true)  /* prisma_run with a table (the headline) */ \
+    X(Explore,       "explore",        false, false, 1,   false, false) /* prisma_run_explore */        \
+    X(ExploreMlp,    "explore_mlp",    true,  false, 1,   false, false)                                 \
+    X(Lightq,        "lightq",         true,  false, 0,   true,  false) /* PRISMA_POLICY_DQN_LITE ... _DQN_LIGHTER_3 */ \
+    X(ExploreLightq, "explore_lightq", true,  false, 1,   true,  false)                                 \
+    X(Smart,         "smart",          false, false, 2,   false, false) /* prisma_run_explore_smart */  \
+    X(SmartMlp,      "smart_mlp",      true,  false, 2,   false, false)                                 \
+    X(SmartLightq,   "smart_lightq",   true,  false, 2,   true,  false)                                 \
+    X(Stoch,         "stoch",          false, false, 3,   false, true)  /* prisma_run_stochastic */
+#define PRISMA_SET_ID_(ID_, ...) kSet##ID_,
+enum StepSet { PRISMA_STEP_SETS(PRISMA_SET_ID_) kNumStepSets };
+struct StepSetInfo { const char* name; bool mlp, ctrl; int expl; bool lq, fused; };
+#define PRISMA_SET_ROW_(ID_, ...) { __VA_ARGS__ },
+constexpr StepSetInfo kStepSets[kNumStepSets] = { PRISMA_STEP_SETS(PRISMA_SET_ROW_) };
+// The set's kernel for an env's slot counts and overlay kind, or null (fused: tunnelled overlays;
+// every set: a shape outside PRISMA_STEP_SHAPES).  It dispatches to the set's translation unit,
+// which defines its specialisation of prisma_pick_step_set with PRISMA_TU_STEP_SET.
+const void* prisma_pick_step(StepSet set, int fs, int ls, bool tun);
+template <StepSet S> const void* prisma_pick_step_set(int fs, int ls, bool tun);
+#define PRISMA_SET_DECL_(ID_, ...) template <> const void* prisma_pick_step_set<kSet##ID_>(int fs, int ls, bool tun);
+PRISMA_STEP_SETS(PRISMA_SET_DECL_)
+
 #if PRISMA_WAVE_TIMES
 // diagnostic build only (scripts/wave_times.py): each replica's wave start / end (s_memrealtime,
 // 100 MHz) and hardware ids of its last launch
@@ -150,88 +186,41 @@ prisma_step_kernel_stoch_t(KParams P) {
 }
 
 // instantiations: flow slots FS in {1,2,4,8} (F <= 512), link slots LS in {1,2,4} (L <= 256)
-template <int FS, int LS, bool CTRL, bool MLP, bool EXPL = false, bool LQ = false> const void* step_kernel(bool tun) {
-    static_assert(!(EXPL && CTRL), "the exploring instances carry no ctrl paths");
-    static_assert(!LQ || (MLP && !CTRL), "the reduced-model instances are MLP instances without the ctrl paths");
-    return tun ? (const void*)prisma_step_kernel_t<FS, LS, MLP, true, CTRL, EXPL, LQ>
-               : (const void*)prisma_step_kernel_t<FS, LS, MLP, false, CTRL, EXPL, LQ>;
+#define PRISMA_STEP_SHAPES(X) X(1, 1) X(1, 2) X(1, 4) X(2, 1) X(2, 2) X(2, 4) X(4, 1) X(4, 2) X(4, 4) X(8, 1) X(8, 2) X(8, 4)
+
+// the kernel of set S for <FS, LS, TUN> (tun: tunnelled-overlay instance; identity overlays run
+// code without the tunnel paths), by its row of kStepSets
+template <StepSet S, int FS, int LS, bool TUN> const void* step_kernel() {
+    constexpr StepSetInfo I = kStepSets[S];
+    static_assert(!(I.expl && I.ctrl), "the exploring instances carry no ctrl paths");
+    static_assert(!I.lq || (I.mlp && !I.ctrl), "the reduced-model instances are MLP instances without the ctrl paths");
+    if constexpr (I.expl == 3) return (const void*)prisma_step_kernel_stoch_t<FS, LS, TUN, I.ctrl>;
+    else if constexpr (I.expl == 2) return (const void*)prisma_step_kernel_smart_t<FS, LS, I.mlp, TUN, I.lq>;
+    else if constexpr (I.fused) return TUN ? nullptr : (const void*)prisma_step_kernel_fused_t<FS, LS, false, I.ctrl>;
+    else return (const void*)prisma_step_kernel_t<FS, LS, I.mlp, TUN, I.ctrl, I.expl == 1, I.lq>;
 }
 
-// tun: tunnelled-overlay instance (identity overlays run code without the tunnel paths).
-// One translation unit per (CTRL, MLP) instance set, so the sets compile in parallel:
-// prisma_engine.hip (CTRL, tables), prisma_engine_mlp.hip (CTRL, MLP), prisma_engine_lite.hip
-// and prisma_engine_lite_mlp.hip (without the ctrl paths), prisma_engine_explore.hip and
-// prisma_engine_explore_mlp.hip (EXPL, without the ctrl paths), prisma_engine_lightq.hip and
-// prisma_engine_explore_lightq.hip (LQ, without the ctrl paths), prisma_engine_smart.hip,
-// prisma_engine_smart_mlp.hip and prisma_engine_smart_lightq.hip (SMART, without the ctrl paths),
-// prisma_engine_fused.hip (FUSED tables, without the ctrl paths), prisma_engine_stoch.hip (STOCH)
-template <bool CTRL, bool MLP, bool EXPL = false, bool LQ = false>
-static const void* pick_step(int fs, int ls, bool tun) {
+// (a template, so only the translation unit that names a set instantiates its kernels)
+template <StepSet S> static const void* pick_step(int fs, int ls, bool tun) {
 #ifdef PRISMA_DEV_HEADLINE
-    // register-allocation experiments only: compile the headline instance alone -- the fused
-    // one (pick_step_fused), or with -DPRISMA_DEV_GENERAL the general one prisma_step launches
+    // register-allocation experiments only (scripts/asm_headline.sh): compile the headline instance
+    // alone -- the fused one, or with -DPRISMA_DEV_GENERAL the general one prisma_step launches
 #ifdef PRISMA_DEV_GENERAL
-    return (!CTRL && !MLP && !EXPL && !LQ && fs == 2 && ls == 1 && !tun) ? (const void*)prisma_step_kernel_t<2, 1, false, false, false>
-                                                         : nullptr;
+    constexpr StepSet kDev = kSetLite;
 #else
-    return nullptr;
+    constexpr StepSet kDev = kSetFused;
 #endif
+    if constexpr (S == kDev) return (fs == 2 && ls == 1 && !tun) ? step_kernel<S, 2, 1, false>() : nullptr;
+    else return nullptr;
 #else
-#define PK(F_, L_) if (fs == F_ && ls == L_) return step_kernel<F_, L_, CTRL, MLP, EXPL, LQ>(tun);
-    PK(1, 1) PK(1, 2) PK(1, 4) PK(2, 1) PK(2, 2) PK(2, 4) PK(4, 1) PK(4, 2) PK(4, 4) PK(8, 1) PK(8, 2) PK(8, 4)
+#define PK(F_, L_) if (fs == F_ && ls == L_) return tun ? step_kernel<S, F_, L_, true>() : step_kernel<S, F_, L_, false>();
+    PRISMA_STEP_SHAPES(PK)
 #undef PK
     return nullptr;
 #endif
 }
-
-// (a template as pick_step is, so only the translation unit that calls it instantiates the kernels)
-template <bool CTRL>
-static const void* pick_step_fused(int fs, int ls, bool tun) {
-    static_assert(!CTRL, "the fused-only instances carry no ctrl paths");
-#ifdef PRISMA_DEV_HEADLINE
-#ifdef PRISMA_DEV_GENERAL
-    return nullptr;
-#else
-    return (fs == 2 && ls == 1 && !tun) ? (const void*)prisma_step_kernel_fused_t<2, 1, false, CTRL> : nullptr;
-#endif
-#else
-    if (tun) return nullptr;
-#define PK(F_, L_) if (fs == F_ && ls == L_) return (const void*)prisma_step_kernel_fused_t<F_, L_, false, CTRL>;
-    PK(1, 1) PK(1, 2) PK(1, 4) PK(2, 1) PK(2, 2) PK(2, 4) PK(4, 1) PK(4, 2) PK(4, 4) PK(8, 1) PK(8, 2) PK(8, 4)
-#undef PK
-    return nullptr;
-#endif
-}
-
-template <bool MLP, bool LQ = false>
-static const void* pick_step_smart(int fs, int ls, bool tun) {
-#ifdef PRISMA_DEV_HEADLINE
-    return nullptr;
-#else
-#define PK(F_, L_)                                                                                      \
-    if (fs == F_ && ls == L_)                                                                           \
-        return tun ? (const void*)prisma_step_kernel_smart_t<F_, L_, MLP, true, LQ>                     \
-                   : (const void*)prisma_step_kernel_smart_t<F_, L_, MLP, false, LQ>;
-    PK(1, 1) PK(1, 2) PK(1, 4) PK(2, 1) PK(2, 2) PK(2, 4) PK(4, 1) PK(4, 2) PK(4, 4) PK(8, 1) PK(8, 2) PK(8, 4)
-#undef PK
-    return nullptr;
-#endif
-}
-
-template <bool CTRL>
-static const void* pick_step_stoch(int fs, int ls, bool tun) {
-#ifdef PRISMA_DEV_HEADLINE
-    return nullptr;
-#else
-#define PK(F_, L_)                                                                                      \
-    if (fs == F_ && ls == L_)                                                                           \
-        return tun ? (const void*)prisma_step_kernel_stoch_t<F_, L_, true, CTRL>                        \
-                   : (const void*)prisma_step_kernel_stoch_t<F_, L_, false, CTRL>;
-    PK(1, 1) PK(1, 2) PK(1, 4) PK(2, 1) PK(2, 2) PK(2, 4) PK(4, 1) PK(4, 2) PK(4, 4) PK(8, 1) PK(8, 2) PK(8, 4)
-#undef PK
-    return nullptr;
-#endif
-}
+#define PRISMA_TU_STEP_SET(S)                                                                           \
+    template <> const void* prisma_pick_step_set<S>(int fs, int ls, bool tun) { return pick_step<S>(fs, ls, tun); }
 
 #if PRISMA_WAVE_TIMES
 #define PRISMA_TU_WAVE_TIMES(NAME)                                                                      \

@@ -191,6 +191,13 @@ def test_episode_boundary_inside_a_launch(oracle_mod):
     eng.close()
 
 
+# the library's refusals, whole: status PRISMA_ERR_CONFIG (-1) and the text
+REFUSAL_MEMORY = "prisma error -1: prisma_run_explore: the memory-resident engine has no exploring instances"
+REFUSAL_CTRL = ("prisma error -1: prisma_run_explore: this env runs the step kernels with the ctrl paths (train, "
+                "notify_dest, ns-3 streams, or a tunnelled overlay with log_capacity >= 2^18), which have no exploring "
+                "instances")
+
+
 @pytest.mark.parametrize("kw", [dict(train=1), dict(rng="ns3"), dict(engine=PRISMA_ENGINE_MEMORY)],
                          ids=["train", "ns3-rng", "memory-engine"])
 def test_refusals(kw):
@@ -200,8 +207,9 @@ def test_refusals(kw):
     assert eng.kernel_info()["ctrl"] == 1 or eng.engine_kind == PRISMA_ENGINE_MEMORY
     eng.reset(0)
     dev = torch.from_numpy(sp_next_hop_table(topo)).cuda()
-    with pytest.raises(PrismaError, match="prisma_run_explore"):
+    with pytest.raises(PrismaError) as err:
         eng.run(dev, 100, explore=0.1)
+    assert str(err.value) == (REFUSAL_MEMORY if "engine" in kw else REFUSAL_CTRL)
     eng.run(dev, 100)                                      # the plain run still works
     torch.cuda.synchronize()
     cnt = eng.counters()

@@ -245,6 +245,18 @@ def test_explore(oracle_mod):
         assert len(z) and np.array_equal(a, z["action"])
 
 
+def test_explore_tunnelled_overlay(oracle_mod):
+    """The exploring reduced-model instances of a tunnelled overlay (the explore_lightq slot with
+    TUN): the small full-mesh overlay on Abilene, the overlay nodes exploring."""
+    topo = _topo("overlay_full_mesh_3n_abilene", 20.0)
+    params = engine_params(topo, sim_time_s=30.0, replica_base=5, log_capacity=LOG)
+    eps = np.where(topo.degrees > 0, 0.3, 0.0)
+    refs = _run_case(oracle_mod, topo, params, "buffer_lighter", label="overlay mesh explore", eps=eps,
+                     kernel=dict(tunnels=1))
+    for ref in refs:
+        assert ref.explored > 0 and ref.changed > 0 and ref.explored < ref.hops
+
+
 # ---- 8. train_fused ------------------------------------------------------------------------------
 def test_train_fused():
     from prisma_amd.env import VecRoutingEnv
@@ -275,6 +287,19 @@ def test_train_fused():
 
 
 # ---- 9. refusals ---------------------------------------------------------------------------------
+# the library's refusals, whole: status PRISMA_ERR_CONFIG (-1) and the text.  An exploring run is
+# refused by prisma_run_explore before the model is looked at.
+REFUSAL_MEMORY = ("prisma error -1: PRISMA_POLICY_DQN_LITE ... _DQN_LIGHTER_3: the memory-resident engine has no "
+                  "instances with the reduced DQN-buffer models")
+REFUSAL_CTRL = ("prisma error -1: PRISMA_POLICY_DQN_LITE ... _DQN_LIGHTER_3: this env runs the step kernels with the "
+                "ctrl paths (train, notify_dest, ns-3 streams, or a tunnelled overlay with log_capacity >= 2^18), which "
+                "have no instances with the reduced DQN-buffer models")
+REFUSAL_EXPLORE_MEMORY = "prisma error -1: prisma_run_explore: the memory-resident engine has no exploring instances"
+REFUSAL_EXPLORE_CTRL = ("prisma error -1: prisma_run_explore: this env runs the step kernels with the ctrl paths (train, "
+                        "notify_dest, ns-3 streams, or a tunnelled overlay with log_capacity >= 2^18), which have no "
+                        "exploring instances")
+
+
 @pytest.mark.parametrize("kw", [dict(train=1), dict(engine=PRISMA_ENGINE_MEMORY)], ids=["train", "memory-engine"])
 def test_refusals(oracle_mod, kw):
     topo = _topo("abilene", 1.0)
@@ -285,10 +310,12 @@ def test_refusals(oracle_mod, kw):
         eng.reset(0)
         for kind in NEW_KINDS:
             w = torch.from_numpy(_net(topo, kind)[1]).cuda()
-            with pytest.raises(PrismaError, match=r"prisma error -1: PRISMA_POLICY_DQN_LITE"):
+            with pytest.raises(PrismaError) as err:
                 eng.run(w, 100, model=kind)
-            with pytest.raises(PrismaError, match=r"prisma error -1"):
+            assert str(err.value) == (REFUSAL_MEMORY if "engine" in kw else REFUSAL_CTRL)
+            with pytest.raises(PrismaError) as err:
                 eng.run(w, 100, model=kind, explore=0.1)
+            assert str(err.value) == (REFUSAL_EXPLORE_MEMORY if "engine" in kw else REFUSAL_EXPLORE_CTRL)
         # the DQN-buffer model still runs here, with and without model="buffer"
         wb = _net(topo, "buffer")[1]
         dev = torch.from_numpy(wb).cuda()

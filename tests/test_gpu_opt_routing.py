@@ -321,6 +321,14 @@ def _raw(eng, tab_ptr, words, hops=100):
     return E._lib.prisma_run_stochastic(eng.h, tab_ptr, words, hops, None)
 
 
+# the library's refusals, whole: status PRISMA_ERR_CONFIG (-1) and the text
+REFUSAL_MEMORY = ("prisma error -1: prisma_run_stochastic: the memory-resident engine has no instances with stochastic "
+                  "routing")
+REFUSAL_CTRL = ("prisma error -1: prisma_run_stochastic: this env runs the step kernels with the ctrl paths (train, "
+                "notify_dest, ns-3 streams, or a tunnelled overlay with log_capacity >= 2^18), which have no instances "
+                "with stochastic routing")
+
+
 @pytest.mark.parametrize("kw", [dict(train=1), dict(engine=PRISMA_ENGINE_MEMORY)], ids=["train", "memory-engine"])
 def test_refuses_by_config(kw):
     topo = _topo("abilene")
@@ -330,8 +338,9 @@ def test_refuses_by_config(kw):
     eng.reset(0)
     tab = _device_table(eng, optrouting.ecmp_routing(topo))
     assert _raw(eng, tab.data_ptr(), tab.numel()) == -1                        # PRISMA_ERR_CONFIG
-    with pytest.raises(PrismaError, match="prisma_run_stochastic"):
+    with pytest.raises(PrismaError) as err:
         eng.run_stochastic(tab, 100)
+    assert str(err.value) == (REFUSAL_MEMORY if "engine" in kw else REFUSAL_CTRL)
     eng.run(torch.from_numpy(sp_next_hop_table(topo)).cuda(), 100)         # the engine still runs
     torch.cuda.synchronize()
     cnt = eng.counters()

@@ -210,6 +210,33 @@ def test_tunnelled_overlay(oracle_mod):
     eng.close()
 
 
+@pytest.mark.parametrize("kind", ["buffer", "buffer_lighter_3"])
+def test_tunnelled_overlay_models(oracle_mod, kind):
+    """The smart_mlp and smart_lightq slots of a tunnelled overlay (the table one: above): the
+    small full-mesh overlay on Abilene, a whole episode."""
+    from prisma_amd.policies import StackedQNet
+    import lightq_util as LQ
+    topo = Topology.example("overlay_full_mesh_3n_abilene", 0, 10.0)
+    params = engine_params(topo, sim_time_s=1.5, log_capacity=LOG)
+    eps = np.where(topo.degrees > 0, 0.3, 0.0)
+    w = StackedQNet(topo, kind, seed=11).pack()
+    wh = w.cpu().numpy()
+    policy = ("mlp", wh) if kind == "buffer" else ("host", (LQ.HostMLP(oracle_mod, topo, kind), wh))
+    eng = PrismaEngine(topo, params, 2)
+    ki = eng.kernel_info()
+    assert ki["tunnels"] == 1 and ki["ctrl"] == 0
+    hist = eng.new_action_history()
+    eng.reset(0)
+    eng.run(w, HUGE, explore=eps, model=kind, action_history=hist)
+    refs = _reference(oracle_mod, topo, params, 2, explore.thresholds(eps), policy)
+    for ref in refs:
+        print(f"overlay mesh {kind}: {ref.explored} explored, {ref.changed} changed, {ref.differing} differ, "
+              f"{int(ref.counters()['ov_lost'])} lost")
+        assert ref.explored > 100 and ref.changed > 30 and ref.differing > 10
+    _compare_whole_episode(eng, refs, hist, f"overlay mesh {kind}")
+    eng.close()
+
+
 def test_episode_boundary_inside_a_launch(oracle_mod):
     topo = _topo("abilene")
     params = engine_params(topo, sim_time_s=1.0, auto_reset=1, log_capacity=LOG)
@@ -278,6 +305,13 @@ def test_wide_star(oracle_mod, d):
     eng.close()
 
 
+# the library's refusals, whole: status PRISMA_ERR_CONFIG (-1) and the text
+REFUSAL_MEMORY = "prisma error -1: prisma_run_explore_smart: the memory-resident engine has no exploring instances"
+REFUSAL_CTRL = ("prisma error -1: prisma_run_explore_smart: this env runs the step kernels with the ctrl paths (train, "
+                "notify_dest, ns-3 streams, or a tunnelled overlay with log_capacity >= 2^18), which have no exploring "
+                "instances")
+
+
 @pytest.mark.parametrize("kw", [dict(train=1), dict(rng="ns3"), dict(engine=PRISMA_ENGINE_MEMORY)],
                          ids=["train", "ns3-rng", "memory-engine"])
 def test_refusals(kw):
@@ -288,8 +322,9 @@ def test_refusals(kw):
     eng.reset(0)
     dev = torch.from_numpy(sp_next_hop_table(topo)).cuda()
     hist = eng.new_action_history()
-    with pytest.raises(PrismaError, match="prisma_run_explore_smart"):
+    with pytest.raises(PrismaError) as err:
         eng.run(dev, 100, explore=0.1, action_history=hist)
+    assert str(err.value) == (REFUSAL_MEMORY if "engine" in kw else REFUSAL_CTRL)
     assert bool((hist == 1).all())
     eng.run(dev, 100)                                      # the plain run still works
     torch.cuda.synchronize()
