@@ -68,6 +68,31 @@ def _fma_step(h64, w64, acc64):
     return s.astype(np.float32).astype(np.float64)
 
 
+def _fma_chain(h64, W64):
+    """The fmaf chains of a dense layer before its bias: h64 [n, in] and W64 [in, out] (float64
+    arrays that hold float32 values) -> [n, out], every unit's chain in input order from +0, each
+    link as _fma_step.  The plain float64 sums of the whole chain first, tested for _fma_step's
+    doubtful cases all at once afterwards: a chain without one is what _fma_step gives link by link
+    (up to the first doubtful link both see the same sums), any other is redone link by link."""
+    if h64.shape[0] > 256:                                 # (bounds the [n, in, out] temporaries)
+        return np.concatenate([_fma_chain(h64[k:k + 256], W64) for k in range(0, h64.shape[0], 256)])
+    prod = h64[:, :, None] * W64[None, :, :]               # exact: 24 + 24 mantissa bits
+    sums = np.empty_like(prod)
+    acc = np.zeros((h64.shape[0], W64.shape[1]), dtype=np.float64)
+    for i in range(W64.shape[0]):
+        s = sums[:, i]
+        np.add(prod[:, i], acc, out=s)
+        acc = s.astype(np.float32).astype(np.float64)
+    bits = sums.view(np.int64)
+    tiny = ((bits & _MAG) - 1).view(np.uint64) < _TINY_BITS_1
+    if not (((bits & _LOW29) == _HALF) | tiny).any():
+        return acc
+    acc = np.zeros((h64.shape[0], W64.shape[1]), dtype=np.float64)
+    for i in range(W64.shape[0]):
+        acc = _fma_step(h64[:, i:i + 1], W64[i][None, :], acc)
+    return acc
+
+
 def random_obs(topo, v, n, rng):
     """n observations at node v: uniform buffer values, with all-equal rows, zero rows and rows at
     the largest buffer value mixed in."""
@@ -132,10 +157,7 @@ class HostMLP:
 
     def _dense(self, h64, W64, b64):
         """h64 [n, in], W64 [in, out], b64 [out]: the fmaf chains in input order, bias last, ELU."""
-        acc = np.zeros((h64.shape[0], W64.shape[1]), dtype=np.float64)
-        for i in range(W64.shape[0]):
-            acc = _fma_step(h64[:, i:i + 1], W64[i][None, :], acc)
-        return self._elu((acc.astype(np.float32) + b64.astype(np.float32)[None, :]).astype(np.float64))
+        return self._elu((_fma_chain(h64, W64).astype(np.float32) + b64.astype(np.float32)[None, :]).astype(np.float64))
 
     def _q_node(self, P, v, obs):
         """Q [n, deg] of n observations (uint32 [n, >= 1 + deg]) at node v."""

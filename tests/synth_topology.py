@@ -1,6 +1,8 @@
 """Synthetic topologies that reach every (flow_slots, link_slots) instance of the register-resident
 step kernel at its slot boundaries, and the case matrix tests/test_instance_matrix.py (CPU: the
-plan and the oracle's own run) and tests/test_gpu_instances.py (GPU parity) both import; then the
+plan and the oracle's own run) and tests/test_gpu_instances.py (GPU parity) both import, with a
+second variant table for the newer instance sets (SET_VARIANTS: tests/test_set_instance_matrix.py
+and tests/test_gpu_set_instances.py); then the
 same for the memory-resident engine's 64-ary event tree (MEMORY_CASES, at the end of the file:
 tests/test_mem_instance_matrix.py and tests/test_gpu_mem_instances.py).
 
@@ -168,7 +170,12 @@ _STAR_LDS = {17: (1, 0)}
 STARS = {f"star{d}": _c("star", (d, min(64, d * (d - 1))), (1, _STAR_LS[d]), _STAR_LDS.get(d, (1, 1)),
                         rate=int(0.6 * 0.9 * LINK_BPS * 55 / 64) if d == 55 else None)
          for d in STAR_DEGREES}
-CASES = {**IDENTITY, **TUNNELLED, **STARS}
+# l256d_f130's graph with 257 flows: shape (8, 4) with the action table in LDS (40 nodes: 1 600 B),
+# where l256_f512's 4 096 B stay in HBM -- the one way to a fused-only table instance of that shape.
+# Beside IDENTITY, so of the GPU matrices only tests/test_gpu_set_instances.py runs it, on that instance
+LDS_TABLE_8_4 = "l256d_f257"
+EXTRA = {LDS_TABLE_8_4: _c("synth", (40, 108, 257), (8, 4), (1, 1), rate=int(0.5 * default_rate(108, 257)))}
+CASES = {**IDENTITY, **TUNNELLED, **STARS, **EXTRA}
 
 # inner underlay nodes as overlay nodes: a ping-back crosses an overlay node of lower degree within
 # the first ping rounds, so every replica ends on PRISMA_EBIT_PINGIDX (tests/test_error_flags.py);
@@ -193,6 +200,29 @@ LOG = 8192
 VARIANTS = {"lite_table": (0, 0, 0), "ctrl_table": (0, 1, 0), "lite_mlp": (1, 0, 0), "ctrl_mlp": (1, 1, 0),
             "explore_table": (0, 0, 1), "explore_mlp": (1, 0, 1)}
 PK_SHAPES = [(fs, ls) for fs in (1, 2, 4, 8) for ls in (1, 2, 4)]
+
+# the sets added after VARIANTS (tests/test_set_instance_matrix.py on the CPU, tests/test_gpu_set_instances.py
+# on the GPU): the step-kernel set the run launches, its policy ("table": the SP table; a DQN-buffer
+# family kind: StackedQNet(topo, kind, seed=MLP_SEED); "stoch": optrouting.path_split_routing(topo, 3,
+# SEED)), whether node_eps explores, whether a history of ones weights the exploring picks, and the hops
+# per case, over 2 launches on the GPU.  The exploring variants take 4 000: a quarter of the nodes
+# explore at every decision, packets wander, and on the 64-node cases 3 000 hops end at 0.53 - 0.6 s,
+# before the third ping round (0.6 s); 4 000 reach it on every case and replica
+EXPLORE_H = 4000
+
+
+def _v(set_, policy, hops, explore=0, smart=0):
+    return dict(set=set_, policy=policy, hops=hops, explore=explore, smart=smart)
+
+
+SET_VARIANTS = {
+    "lightq": _v("lightq", "buffer_lite", H),
+    "explore_lightq": _v("explore_lightq", "buffer_lighter_3", EXPLORE_H, explore=1),
+    "smart_table": _v("smart", "table", EXPLORE_H, explore=1, smart=1),
+    "smart_mlp": _v("smart_mlp", "buffer", EXPLORE_H, explore=1, smart=1),
+    "smart_lightq": _v("smart_lightq", "buffer_lighter_3", EXPLORE_H, explore=1, smart=1),
+    "stoch": _v("stoch", "stoch", H),
+}
 
 
 @functools.lru_cache(maxsize=None)
@@ -224,6 +254,56 @@ def case_params(name, **kw):
     args.update(CASES[name]["params"])
     args.update(kw)
     return engine_params(build(name), **args)
+
+
+def node_eps(topo):
+    """Per-node epsilons of the exploring variants: 0, 1, 0.3 and 0.05 by overlay index, 0 off the
+    overlay (tests/test_gpu_instances.py's _eps)."""
+    eps = np.zeros(topo.n_nodes)
+    eps[topo.overlay_nodes] = [(0.0, 1.0, 0.3, 0.05)[i % 4] for i in range(topo.n_overlay)]
+    return eps
+
+
+@functools.lru_cache(maxsize=None)
+def case_table(name):
+    from prisma_amd.topology import sp_next_hop_table
+    return sp_next_hop_table(build(name))
+
+
+@functools.lru_cache(maxsize=None)
+def case_net(name, kind):
+    """(torch model on the CPU, its packed weights as numpy) of a case and a DQN-buffer family kind."""
+    from prisma_amd.policies import StackedQNet
+    net = StackedQNet(build(name), kind, seed=MLP_SEED, device="cpu")
+    return net, net.pack().numpy()
+
+
+@functools.lru_cache(maxsize=None)
+def case_routing(name):
+    """The stoch variant's routing matrix, float64 [NO, NO, T] in the reference's edge order."""
+    from prisma_amd import optrouting
+    return optrouting.path_split_routing(build(name), 3, seed=SEED)
+
+
+def set_variant_inputs(name, variant):
+    """What a SET_VARIANTS run of a case takes, the same objects on the CPU and on the GPU:
+    dict(policy=the SP table | packed fp32 weights | the routing matrix, kind=the model kind or None,
+    net=the torch model or None, eps=per-node epsilons or None, thr=their thresholds or None)."""
+    from prisma_amd import explore
+    v = SET_VARIANTS[variant]
+    topo = build(name)
+    out = dict(kind=None, net=None, eps=None, thr=None)
+    if v["policy"] == "table":
+        out["policy"] = case_table(name)
+    elif v["policy"] == "stoch":
+        out["policy"] = case_routing(name)
+    else:
+        out["kind"] = v["policy"]
+        out["net"], out["policy"] = case_net(name, v["policy"])
+    if v["explore"]:
+        out["eps"] = node_eps(topo)
+        out["thr"] = explore.thresholds(out["eps"])
+    return out
 
 
 def last_switch_slot(topo):

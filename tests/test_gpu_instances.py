@@ -6,7 +6,13 @@ laid out and not, big signalling at 64 flows, and the stars on the memory-reside
 
 Every case: 3 replicas from replica_base 7, a 6-s episode, 3 000 hops over 2 launches, a log of
 8 192 records; tests/test_instance_matrix.py checks on the CPU that each case's run reaches the
-boundary slots."""
+boundary slots.
+
+S.VARIANTS drives seven of the thirteen step-kernel sets (ctrl, ctrl_mlp, lite, lite_mlp, explore,
+explore_mlp, and fused where the table sits in LDS).  The other six -- lightq, explore_lightq, smart,
+smart_mlp, smart_lightq, stoch -- have a variant table of their own, S.SET_VARIANTS, run over the
+same cases by tests/test_gpu_set_instances.py; the ledger of which (set, shape, overlay kind) the two
+tables reach together is tests/test_set_instance_matrix.py's test_ledger_every_set_reaches_every_shape."""
 import functools
 
 import numpy as np

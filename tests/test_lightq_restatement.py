@@ -78,6 +78,36 @@ def test_fmaf_emulation_half_way_cases():
     assert np.any(plain.view(np.uint32) != want.view(np.uint32))
 
 
+def test_fma_chain_equals_its_links():
+    """A dense layer's chains (the plain float64 sums first, the doubtful links tested afterwards)
+    against fmaf32 link by link: random layers, more rows than one chunk, and a layer whose second
+    link lands on an fp32 midpoint, which only the rounding to odd gets right."""
+    rng = np.random.default_rng(2)
+
+    def links(h, W):
+        acc = np.zeros((h.shape[0], W.shape[1]), dtype=np.float32)
+        for i in range(W.shape[0]):
+            acc = LQ.fmaf32(h[:, i:i + 1], W[i][None, :], acc)
+        return acc
+
+    for n, n_in, n_out in ((1, 40, 32), (7, 64, 64), (300, 9, 5)):
+        h = rng.standard_normal((n, n_in)).astype(np.float32)
+        W = rng.standard_normal((n_in, n_out)).astype(np.float32)
+        got = LQ._fma_chain(h.astype(np.float64), W.astype(np.float64)).astype(np.float32)
+        assert np.array_equal(got.view(np.uint32), links(h, W).view(np.uint32)), (n, n_in, n_out)
+    # link 0 leaves c = 1 + 2^-23 in the accumulator; link 1 adds a b = 2^-24 (1 - 2^-40): half an ulp
+    # of c less a sliver that a float64 sum cannot hold
+    a, b = np.float32(2.0 ** -12 * (1 + 2.0 ** -20)), np.float32(2.0 ** -12 * (1 - 2.0 ** -20))
+    h = np.array([[1.0, a, 0.5]], dtype=np.float32)
+    W = np.array([[1 + 2.0 ** -23, 0.25], [b, b], [0.0, 1.0]], dtype=np.float32)
+    plain = ((h[:, :1].astype(np.float64) * W[0] + 0.0).astype(np.float32).astype(np.float64)
+             + h[:, 1:2].astype(np.float64) * W[1]).astype(np.float32)
+    want = links(h[:, :2], W[:2])
+    assert plain.view(np.uint32)[0, 0] != want.view(np.uint32)[0, 0]          # (the case does need it)
+    got = LQ._fma_chain(h.astype(np.float64), W.astype(np.float64)).astype(np.float32)
+    assert np.array_equal(got.view(np.uint32), links(h, W).view(np.uint32))
+
+
 # ---- 2. the restatement at (32, 64, 2) is the oracle's ------------------------------------
 @pytest.mark.parametrize("name", ["abilene", "geant"])
 def test_restatement_equals_oracle_at_buffer_widths(oracle_mod, name):
