@@ -591,6 +591,67 @@ typedef struct prisma_replay {
 int prisma_ingest_transitions(prisma_env_t* env, int64_t* consumed, const prisma_replay_t* rings,
                               void* stream);
 
+/*
+ * The stored Q networks a replay batch's bootstrap targets are computed against
+ * (prisma_replay_targets): n_gen weight generations of one model, each a packed fp32 network set
+ * (row-major, x @ W, N = n_nodes, D = max_deg, rows by underlay id, (B, H, NH) as in the table
+ * above).  The DQN-buffer kinds take exactly the layouts of PRISMA_POLICY_DQN_BUFFER ...
+ * _DQN_LIGHTER_3 (StackedQNet.pack()).  PRISMA_QMODEL_ROUTING is DQN_routing_model
+ * (models.py:360-392), the 64-wide layout without the buffers branch:
+ *   W1[N][N][32] b1[N][32] W2[N][32][64] b2[N][64] W3[N][64][64] b3[N][64] W4[N][64][D] b4[N][D]
+ */
+#define PRISMA_QMODEL_ROUTING  0
+typedef struct prisma_qnets {
+    const float* const* weights;  /* device array [n_gen] of device pointers, one packed network set each */
+    int32_t  n_gen;               /* >= 1 */
+    int32_t  model;               /* PRISMA_QMODEL_ROUTING (0), or PRISMA_POLICY_DQN_BUFFER ... _DQN_LIGHTER_3 */
+    const int32_t* gen_of;        /* device int32 [n_replicas][T], T and row[] of prisma_action_history_layout:
+                                     the generation that (replica r, node u, action a) reads, at
+                                     gen_of[r][row[u] + a]; NULL = generation 0 everywhere */
+} prisma_qnets_t;
+
+/*
+ * The bootstrap targets of a sampled replay batch against every stored generation: what
+ * ReplayBuffers.sample_full() followed by QRoutingTrainer.targets() computes, as one launch on
+ * `stream` with no host read.  idx: device int64 [N][batch], a ring slot per (node, batch
+ * position).  Outputs are device arrays with row i = u * batch + b: obs_out int32 [N * batch][W],
+ * action_out int64 [N * batch], target_out float [N * batch], status_out uint8 [N * batch];
+ * obs_out, action_out and status_out may be NULL.  Either engine: the call reads only the rings,
+ * the weights and the env's overlay CSR (row[], the next node and the back action per (u, a), a
+ * small device table built from the env's host topology at the first call and freed by
+ * prisma_destroy).
+ *
+ * The rule, for row i = (u, b) with s = idx[u][b]:
+ *   Slot.      s outside [0, rings->size): obs_out[i] = zeros, action_out[i] = 0, target = +0,
+ *              status = 2; nothing of the rings is read.
+ *   Gather.    a = rings->action[u][s], rew, done, r = rings->replica[u][s], next_obs[u][s][:];
+ *              obs_out[i] = rings->obs[u][s][:], action_out[i] = a.
+ *   Not evaluable.  a outside [0, deg(u)) (every node without an agent), r outside
+ *              [0, n_replicas), or the generation g = gen_of[r][row[u] + a] outside [0, n_gen); or,
+ *              for an item that is not done, next_obs[0] (the one-hot input) outside [0, N):
+ *              target = rew, status = 2.  No out-of-range address is ever formed, and the value
+ *              is whatever finite reward the ring holds, never a NaN of the call's making.
+ *   Done.      target = rew, status = 1.
+ *   Otherwise  (status = 0): v = the a-th overlay neighbour of u, bk = the action of v that leads
+ *              back to u (or none); q[0 .. deg(v)) = the fp32 Q values of generation g's network
+ *              at node v on next_obs in the fixed operation order of the in-kernel DQN-buffer
+ *              decision (the routing model takes the same order with the one-hot
+ *              branch alone feeding layer 2);
+ *                best = +inf; for j in 0 .. deg(v) - 1: if j != bk and q[j] < best: best = q[j]
+ *                target = fadd_rn(rew, fmul_rn(gamma, best))
+ *              An empty candidate set gives +inf; a NaN Q never wins (defined, not copied:
+ *              torch's min would propagate it).
+ * Null env, rings, idx, nets, nets->weights or target_out, a null ring array the rule reads,
+ * batch < 1, n_gen < 1, rings->size < 1, model == PRISMA_POLICY_TABLE or unknown, or rings->n_nodes /
+ * rings->obs_width different from the env's: PRISMA_ERR_ARG, nothing is launched.  The arguments
+ * that need no env are checked first.  (Added without an ABI version change: no struct or
+ * signature moved.)
+ */
+int prisma_replay_targets(prisma_env_t* env, const prisma_replay_t* rings, const int64_t* idx,
+                          int32_t batch, const prisma_qnets_t* nets, float gamma,
+                          int32_t* obs_out, int64_t* action_out, float* target_out,
+                          uint8_t* status_out, void* stream);
+
 /* Active-replica compaction (ABI 9) for a batched external policy, which then
  * evaluates only the replicas with a pending decision -- the reference's
  * Forwarder steps only the nodes that were notified (ns3env.py:417-423,

@@ -18,7 +18,7 @@ ENGINE_SOURCES = ["prisma_engine.hip", "prisma_engine_mlp.hip", "prisma_engine_l
                   "prisma_engine_mem.hip", "prisma_engine_explore.hip", "prisma_engine_explore_mlp.hip",
                   "prisma_engine_lightq.hip", "prisma_engine_explore_lightq.hip", "prisma_engine_smart.hip",
                   "prisma_engine_smart_mlp.hip", "prisma_engine_smart_lightq.hip", "prisma_engine_ingest.hip",
-                  "prisma_engine_fused.hip", "prisma_engine_stoch.hip"]
+                  "prisma_engine_fused.hip", "prisma_engine_stoch.hip", "prisma_engine_targets.hip"]
 ENGINE_HEADERS = ["engine_core.h", "engine_layout.h", "numerics.h", "step_kernel.h", "mrg32k3a.h", "prio_ladder.h"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std=c++17",
                # the per-replica counters are bumped by lane 0 only: the atomic optimizer's

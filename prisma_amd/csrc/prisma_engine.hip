@@ -334,6 +334,8 @@ struct prisma_env {
     prisma_kernel_info_t kinfo{};        // the step-kernel instances prisma_create picked
     bool reset_done = false;
     void* d_ingest = nullptr;            // prisma_ingest_transitions' counts and offsets (first use)
+    std::vector<int32_t> ovdst;          // [T] next node (underlay id) of every (node, action), ovrow's order
+    int32_t* d_targets_tab = nullptr;    // prisma_replay_targets' row[N + 1], next node[T], back action[T] (first use)
 };
 
 static thread_local std::string g_err;
@@ -362,6 +364,7 @@ struct OverlayPlan {
     bool tunnels = false;                // false: identity overlay (tunnel t == link t)
     int T = 0, NO = 0, maxdeg = 0, plen = 1;
     std::vector<int32_t> ovrow, ovi, ovnode;
+    std::vector<int32_t> ovdst;          // [T] underlay id of the overlay neighbour an action leads to
     std::vector<uint32_t> tinfo, route;  // route: [N][N] next link | hops << 8
     std::vector<uint32_t> tresp;         // pbd slot base | responder position mask << 16
     int n_resp = 0;                      // ping responders over all tunnels (pbd slots)
@@ -438,6 +441,7 @@ static int plan_overlay(const prisma_topology_t* T, OverlayPlan& OP) {
         OP.ovrow[u + 1] = (int32_t)tsrc.size();
     }
     OP.T = (int)tsrc.size();
+    OP.ovdst.assign(tdst.begin(), tdst.end());
     if (OP.T > (int)kMaxTunnels) return set_err(PRISMA_ERR_CONFIG, "more than 4096 tunnels (12-bit tunnel ids)");
     bool ident = (NO == N);
     for (int t = 0; t < OP.T && ident; ++t) ident = (dist[(size_t)tsrc[t] * N + tdst[t]] == 1);
@@ -1066,6 +1070,7 @@ extern "C" int prisma_create(const prisma_topology_t* topo, const prisma_params_
         OverlayPlan OP;                      // (build_layout has validated the overlay)
         if ((rc = plan_overlay(topo, OP)) != 0) { delete e; return rc; }
         e->ovrow = OP.ovrow;
+        e->ovdst = OP.ovdst;
     }
     size_t sb = (size_t)L.state_bytes * n_replicas;
     size_t lb = (size_t)L.log_cap * L.rec_bytes * n_replicas;
@@ -1456,6 +1461,75 @@ extern "C" int prisma_ingest_transitions(prisma_env_t* e, int64_t* consumed, con
     return PRISMA_OK;
 }
 
+// the replay-batch target kernel (prisma_engine_targets.hip)
+hipError_t prisma_targets_launch(const prisma_replay_t* rings, const int64_t* idx, int32_t batch,
+                                 const prisma_qnets_t* nets, const int32_t* tab, int32_t R, int32_t N, int32_t D,
+                                 int32_t T, int32_t B, int32_t H, int32_t NH, int32_t buffers, float gamma,
+                                 int32_t* obs_out, int64_t* action_out, float* target_out, uint8_t* status_out,
+                                 hipStream_t stream);
+
+extern "C" int prisma_replay_targets(prisma_env_t* e, const prisma_replay_t* rings, const int64_t* idx, int32_t batch,
+                                     const prisma_qnets_t* nets, float gamma, int32_t* obs_out, int64_t* action_out,
+                                     float* target_out, uint8_t* status_out, void* stream) {
+    // what needs no env first, so that a caller without a device gets the same answers
+    if (!rings || !idx || !nets || !target_out)
+        return set_err(PRISMA_ERR_ARG, "prisma_replay_targets: null argument (rings, idx, nets and target_out are required)");
+    if (!nets->weights) return set_err(PRISMA_ERR_ARG, "prisma_replay_targets: null nets->weights");
+    if (batch < 1) return set_err(PRISMA_ERR_ARG, "prisma_replay_targets: batch must be >= 1");
+    if (nets->n_gen < 1) return set_err(PRISMA_ERR_ARG, "prisma_replay_targets: n_gen must be >= 1");
+    int B = 32, H = 64, NH = 2, buffers = 1;                  // (B, H, NH) of include/prisma.h's table
+    switch (nets->model) {
+    case PRISMA_QMODEL_ROUTING: buffers = 0; break;
+    case PRISMA_POLICY_DQN_BUFFER: break;
+    case PRISMA_POLICY_DQN_LITE: B = 16; H = 32; break;
+    case PRISMA_POLICY_DQN_LIGHTER: B = 16; H = 32; NH = 1; break;
+    case PRISMA_POLICY_DQN_LIGHTER_2: B = 8; H = 16; NH = 1; break;
+    case PRISMA_POLICY_DQN_LIGHTER_3: B = 4; H = 8; NH = 1; break;
+    case PRISMA_POLICY_TABLE:
+        return set_err(PRISMA_ERR_ARG, "prisma_replay_targets: model PRISMA_POLICY_TABLE has no Q network");
+    default:
+        return set_err(PRISMA_ERR_ARG, "prisma_replay_targets: unknown model " + std::to_string(nets->model));
+    }
+    if (!rings->obs || !rings->next_obs || !rings->action || !rings->reward || !rings->done || !rings->replica)
+        return set_err(PRISMA_ERR_ARG, "prisma_replay_targets: null ring pointer");
+    if (rings->size < 1) return set_err(PRISMA_ERR_ARG, "prisma_replay_targets: ring size must be >= 1");
+    if (!e) return set_err(PRISMA_ERR_ARG, "prisma_replay_targets: null env");
+    if (rings->obs_width != e->lay.W || rings->n_nodes != e->lay.N)
+        return set_err(PRISMA_ERR_ARG, "prisma_replay_targets: the rings' obs_width = " +
+                                       std::to_string(rings->obs_width) + " / n_nodes = " +
+                                       std::to_string(rings->n_nodes) + " differ from the env's " +
+                                       std::to_string(e->lay.W) + " / " + std::to_string(e->lay.N));
+    (void)hipSetDevice(e->device);
+    const int32_t N = e->lay.N, T = e->ovrow.back();
+    if (!e->d_targets_tab) {
+        // row[N + 1], then per (u, a) in row order the next node and its action back to u (-1: none)
+        std::vector<int32_t> tab((size_t)N + 1 + 2 * (size_t)T);
+        memcpy(tab.data(), e->ovrow.data(), sizeof(int32_t) * ((size_t)N + 1));
+        for (int u = 0; u < N; ++u)
+            for (int t = e->ovrow[u]; t < e->ovrow[u + 1]; ++t) {
+                const int v = e->ovdst[t];
+                int bk = -1;
+                for (int k = e->ovrow[v]; k < e->ovrow[v + 1] && bk < 0; ++k)
+                    if (e->ovdst[k] == u) bk = k - e->ovrow[v];
+                tab[(size_t)N + 1 + t] = v;
+                tab[(size_t)N + 1 + T + t] = bk;
+            }
+        int32_t* d = nullptr;
+        if (!HIP_OK(hipMalloc(&d, tab.size() * sizeof(int32_t))))
+            return set_err(PRISMA_ERR_NOMEM, "hipMalloc failed (targets table)");
+        if (!HIP_OK(hipMemcpy(d, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice))) {
+            (void)hipFree(d);
+            return set_err(PRISMA_ERR_DEVICE, "targets table copy failed");
+        }
+        e->d_targets_tab = d;
+    }
+    hipError_t err = prisma_targets_launch(rings, idx, batch, nets, e->d_targets_tab, e->R, N, e->lay.max_deg, T, B, H,
+                                           NH, buffers, gamma, obs_out, action_out, target_out, status_out,
+                                           (hipStream_t)stream);
+    if (err != hipSuccess) return set_err(PRISMA_ERR_LAUNCH, std::string("targets launch failed: ") + hipGetErrorString(err));
+    return PRISMA_OK;
+}
+
 extern "C" int prisma_expand_actions(prisma_env_t* e, const int32_t* ids, const int32_t* count,
                                      const int32_t* packed_actions, int32_t fill, int32_t* actions_out, void* stream) {
     if (!e || !ids || !count || !packed_actions || !actions_out) return set_err(PRISMA_ERR_ARG, "null argument");
@@ -1511,5 +1585,6 @@ extern "C" void prisma_destroy(prisma_env_t* e) {
     if (e->d_spare) (void)hipFree(e->d_spare);
     if (e->d_rng) (void)hipFree(e->d_rng);
     if (e->d_ingest) (void)hipFree(e->d_ingest);
+    if (e->d_targets_tab) (void)hipFree(e->d_targets_tab);
     delete e;
 }

@@ -96,6 +96,21 @@ class _Replay(C.Structure):
                 ("total", C.c_void_p), ("size", C.c_int64), ("n_nodes", C.c_int32), ("obs_width", C.c_int32)]
 
 
+class _QNets(C.Structure):
+    """prisma_qnets_t: the stored weight generations prisma_replay_targets evaluates."""
+    _fields_ = [("weights", C.c_void_p), ("n_gen", C.c_int32), ("model", C.c_int32), ("gen_of", C.c_void_p)]
+
+
+# replay_targets(..., model=): MODEL_POLICIES' kinds and the routing model (include/prisma.h)
+PRISMA_QMODEL_ROUTING = 0
+TARGET_MODELS = dict({"routing": PRISMA_QMODEL_ROUTING}, **{k: v[0] for k, v in MODEL_POLICIES.items()})
+
+
+def routing_floats(n: int, d: int) -> int:
+    """Length of the packed DQ-routing weights (include/prisma.h PRISMA_QMODEL_ROUTING)."""
+    return n * (n * 32 + 32 + 32 * 64 + 64 + 64 * 64 + 64 + 64 * d + d)
+
+
 class _Plan(C.Structure):
     _fields_ = [("state_bytes", C.c_uint32), ("lds_bytes", C.c_uint32), ("lds_state_bytes", C.c_uint32),
                 ("ring_entries", C.c_uint32), ("record_bytes", C.c_uint32), ("obs_width", C.c_int32),
@@ -108,6 +123,7 @@ EXPORTS = [
     "prisma_read_counters", "prisma_counters_device", "prisma_log_view", "prisma_copy_log",
     "prisma_copy_counters", "prisma_gather_records", "prisma_state_bytes", "prisma_plan", "prisma_destroy",
     "prisma_compact_pending", "prisma_expand_actions", "prisma_kernel_info", "prisma_ingest_transitions",
+    "prisma_replay_targets",
 ]
 
 _lib = None
@@ -176,6 +192,9 @@ def load_library(path: str = None):
                                         C.c_void_p]
     L.prisma_ingest_transitions.restype = C.c_int
     L.prisma_ingest_transitions.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(_Replay), C.c_void_p]
+    L.prisma_replay_targets.restype = C.c_int
+    L.prisma_replay_targets.argtypes = [C.c_void_p, C.POINTER(_Replay), C.c_void_p, C.c_int32, C.POINTER(_QNets),
+                                        C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.prisma_kernel_info.restype = C.c_int
     L.prisma_kernel_info.argtypes = [C.c_void_p, C.POINTER(_KernelInfo)]
     L.prisma_state_bytes.restype = C.c_int
@@ -555,6 +574,63 @@ class PrismaEngine:
                                                                    "replica", "next_idx", "count", "total")],
                         size, n, w)
         _check(_lib.prisma_ingest_transitions(self.h, consumed.data_ptr(), C.byref(rings), _stream_handle(stream)))
+
+    def replay_targets(self, buffers, idx, weights, model: str, gamma: float = 1.0, gen_of=None, stream=None) -> dict:
+        """prisma_replay_targets: the batch ``buffers.sample_full(batch, idx=idx)`` selects and its
+        bootstrap targets against every stored weight generation, in one launch on torch's current
+        stream (or `stream`) with no host read -- the rule is in include/prisma.h.
+
+        idx: device int64 [N, batch] ring slots.  weights: a list of packed device float32 tensors,
+        one per generation (StackedQNet.pack_targets()); model: "routing" or a MODEL_POLICIES kind.
+        gen_of: device int32 [n_replicas, T] (action_history_layout), the generation each (replica,
+        node, action) reads, or None for generation 0 everywhere.  Returns device tensors with row
+        i = u * batch + b: obs int32 [N * batch, W], action int64, target float32 and status uint8
+        (0 evaluated, 1 done, 2 not evaluable).  The pointer array lives on the device and is
+        rebuilt only when the list's addresses change; the tensors are kept alive until the next call."""
+        import torch
+        if model not in TARGET_MODELS:
+            raise PrismaError(f"model must be one of {', '.join(TARGET_MODELS)}")
+        n, size, w = int(buffers.N), int(buffers.size), int(buffers.W)
+        if not torch.is_tensor(idx) or idx.dim() != 2 or idx.shape[0] != n or idx.shape[1] < 1:
+            raise ValueError(f"prisma_replay_targets: idx must be an int64 tensor of shape ({n}, batch >= 1)")
+        batch = int(idx.shape[1])
+        want = [("idx", idx, torch.int64, (n, batch))]
+        for name, dt, shape in (("obs", torch.int32, (n, size, w)), ("next_obs", torch.int32, (n, size, w)),
+                                ("action", torch.int64, (n, size)), ("reward", torch.float32, (n, size)),
+                                ("done", torch.bool, (n, size)), ("replica", torch.int64, (n, size))):
+            want.append((name, getattr(buffers, name), dt, shape))
+        weights = list(weights)
+        if not weights:
+            raise ValueError("prisma_replay_targets: weights must hold at least one packed generation")
+        d = self.topo.max_deg
+        floats = routing_floats(n, d) if model == "routing" else model_floats(model, n, d)
+        for g, t in enumerate(weights):
+            want.append((f"weights[{g}]", t, torch.float32, (floats,)))
+        if gen_of is not None:
+            want.append(("gen_of", gen_of, torch.int32, (self.R, int(self.action_history_layout()[1]))))
+        for name, t, dt, shape in want:
+            if (not torch.is_tensor(t) or t.device != self.torch_device or t.dtype != dt or tuple(t.shape) != shape
+                    or not t.is_contiguous()):
+                raise ValueError(f"prisma_replay_targets: {name} must be a contiguous {dt} tensor of shape "
+                                 f"{shape} on {self.torch_device}")
+        ptrs = tuple(t.data_ptr() for t in weights)
+        if getattr(self, "_targets_ptrs", None) != ptrs:
+            self._targets_ptr_dev = torch.tensor(ptrs, dtype=torch.int64, device=self.torch_device)
+            self._targets_ptrs = ptrs
+        self._targets_keep = (weights, gen_of)
+        rows = n * batch
+        out = {"obs": torch.empty((rows, w), dtype=torch.int32, device=self.torch_device),
+               "action": torch.empty(rows, dtype=torch.int64, device=self.torch_device),
+               "target": torch.empty(rows, dtype=torch.float32, device=self.torch_device),
+               "status": torch.empty(rows, dtype=torch.uint8, device=self.torch_device)}
+        rings = _Replay(*[getattr(buffers, k).data_ptr() for k in ("obs", "next_obs", "action", "reward", "done",
+                                                                   "replica")], None, None, None, size, n, w)
+        nets = _QNets(self._targets_ptr_dev.data_ptr(), len(weights), TARGET_MODELS[model],
+                      gen_of.data_ptr() if gen_of is not None else None)
+        _check(_lib.prisma_replay_targets(self.h, C.byref(rings), idx.data_ptr(), batch, C.byref(nets), float(gamma),
+                                          out["obs"].data_ptr(), out["action"].data_ptr(), out["target"].data_ptr(),
+                                          out["status"].data_ptr(), _stream_handle(stream)))
+        return out
 
     def log_tensor(self, stream=None):
         import torch

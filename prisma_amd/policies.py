@@ -162,6 +162,17 @@ class StackedQNet(torch.nn.Module):
         return torch.cat([p.detach().to(torch.float32).contiguous().flatten() for p in parts])
 
     @torch.no_grad()
+    def pack_targets(self) -> torch.Tensor:
+        """Flat fp32 weights for prisma_replay_targets (PrismaEngine.replay_targets): pack() for the
+        DQN-buffer family; for kind="routing" the 64-wide layout without the buffers branch,
+        W1[N][N][32] b1[N][32] W2[N][32][64] b2[N][64] W3[N][64][64] b3[N][64] W4[N][64][D] b4[N][D]
+        (include/prisma.h PRISMA_QMODEL_ROUTING)."""
+        if self.is_buffer:
+            return self.pack()
+        parts = [p for wn in ("W1", "W2", "W3", "W4") for p in (getattr(self, wn), getattr(self, "b" + wn[1:]))]
+        return torch.cat([p.detach().to(torch.float32).contiguous().flatten() for p in parts])
+
+    @torch.no_grad()
     def argmin_table(self) -> torch.Tensor:
         """[N, N] uint8 action table by underlay ids (node, destination); valid for
         kind='routing' (Q depends on (node, dst) only).  Rows / columns of non-overlay

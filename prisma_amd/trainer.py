@@ -99,7 +99,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .policies import BUFFER_DIMS, StackedQNet
+from .policies import BUFFER_DIMS, StackedQNet, buffer_layer_names
 from .records import EBIT_NAMES
 from .topology import Topology
 
@@ -213,6 +213,19 @@ class ReplayBuffers:
         else:
             out["weights"] = torch.ones((self.N, batch_size), dtype=torch.float64, device=self.device)
         return out
+
+    def sample_idx(self, batch_size: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        """The uniform slots sample_full draws (the same draw from the same generator state)."""
+        r = torch.rand((self.N, batch_size), generator=generator, device=self.device, dtype=torch.float64)
+        return torch.clamp((r * self.count.clamp_min(1)[:, None]).long(), max=self.size - 1)
+
+    def importance_weights(self, idx: torch.Tensor) -> torch.Tensor:
+        """sample_full's ``weights`` for the slots idx [N, batch]."""
+        if self.prioritized:
+            tot = self.tree_sum()
+            return torch.gather(self.prio, 1, idx) / tot.clamp_min(1e-300)[:, None] * \
+                self.count.to(torch.float64)[:, None]
+        return torch.ones(tuple(idx.shape), dtype=torch.float64, device=self.device)
 
     def sample(self, batch_size: int, generator: Optional[torch.Generator] = None):
         s = self.sample_full(batch_size, generator)
@@ -361,6 +374,15 @@ class QRoutingTrainer:
         self.peak_generations = 0
         self._bytes_warned = False
         self._gen_w = {}                             # generation key -> stacked weights
+        # the device path of train_step(engine=): one packed device copy per stored generation (made
+        # when first needed, dropped in _gc), the device gen_of [R, T] and what it was built from
+        self._gen_packed = {}
+        self._t_node = np.repeat(np.arange(N), self.deg_host)                   # (node, action) of column t
+        self._t_act = np.concatenate([np.arange(int(d)) for d in self.deg_host] + [np.zeros(0, dtype=np.int64)]).astype(np.int64)
+        self._gen_of_state = None
+        self._gen_of_dev = None
+        self.gen_of_uploads = 0
+        self.last_batch = None
         self._snap_gen = {}                          # version -> generation key
         self.version = 0
         self._snap_gen[0] = self._capture()
@@ -757,21 +779,77 @@ class QRoutingTrainer:
         best = qn.min(dim=1).values
         return torch.where(done, reward, reward + self.gamma * best)
 
-    def train_step(self) -> Optional[torch.Tensor]:
+    def _check_fused_targets(self):
+        if self.signaling == "target":
+            raise ValueError("fused_targets / train_step(engine=) compute the targets from the stored networks; with "
+                             "signaling_type='target' the buffer already holds them: use the default path")
+
+    def _pack_generation(self, key) -> torch.Tensor:
+        """The packed device copy of a stored generation (StackedQNet.pack_targets()'s layout), made
+        when first needed and dropped in _gc with the generation."""
+        t = self._gen_packed.get(key)
+        if t is None:
+            sd = self._gen_w[key]
+            names = ("W1", "W2", "W3", "W4") if self.kind == "routing" else buffer_layer_names(self.kind)
+            t = torch.cat([sd[n].detach().to(self.device, torch.float32).contiguous().flatten()
+                           for wn in names for n in (wn, "b" + wn[1:])])
+            self._gen_packed[key] = t
+        return t
+
+    def _device_generations(self):
+        """(packed generations, device gen_of int32 [R, T]) for prisma_replay_targets: the stored
+        generations tgt_ver refers to, in _gen_w's order, and for every (replica, node, action) the
+        index of its copy's generation among them, in the action-history layout (hist_row).  gen_of
+        is rebuilt and uploaded only when tgt_ver or the generation set changed since the last upload."""
+        vers = np.unique(self.tgt_ver)
+        needed = {self._snap_gen[int(k)] for k in vers.tolist()}
+        keys = tuple(k for k in self._gen_w if k in needed)
+        last = self._gen_of_state
+        if last is None or last[0] != keys or not np.array_equal(last[1], self.tgt_ver):
+            pos = {k: i for i, k in enumerate(keys)}
+            lut = np.array([pos[self._snap_gen[int(k)]] for k in vers.tolist()], dtype=np.int32)
+            flat = self.tgt_ver[:, self._t_node, self._t_act]                  # [R, T]
+            gen_of = lut[np.searchsorted(vers, flat)]
+            self._gen_of_dev = torch.from_numpy(np.ascontiguousarray(gen_of, dtype=np.int32)).to(self.device)
+            self._gen_of_state = (keys, self.tgt_ver.copy())
+            self.gen_of_uploads += 1
+        return [self._pack_generation(k) for k in keys], self._gen_of_dev
+
+    def train_step(self, engine=None) -> Optional[torch.Tensor]:
         """One gradient step on every node whose buffer received >= batch_size transitions.
-        Returns the per-node mean Huber loss (nan for nodes that did not train)."""
+        Returns the per-node mean Huber loss (nan for nodes that did not train).
+
+        With ``engine`` (a PrismaEngine on the trainer's device with the trainer's replicas) the
+        batch and its targets come from one device pass (PrismaEngine.replay_targets,
+        prisma_replay_targets) instead of sample_full() plus targets(): the same slots and importance
+        weights from the same draws, the targets in the in-kernel decision's fixed fp32 operation
+        order (include/prisma.h states the rule), no host read and one launch for every stored
+        generation.  ``last_batch`` then holds the step's slots, targets, status and generations."""
         N, B = self.N, self.batch_size
         ready = (self.buffers.total >= B) & (self.deg > 0)
+        if engine is not None:
+            self._check_fused_targets()
+            if int(engine.R) != self.R:
+                raise ValueError(f"the engine runs {engine.R} replicas but the trainer was built with n_replicas={self.R}")
         if not bool(ready.any()):
             return None
-        s = self.buffers.sample_full(B, self.gen)
         node = torch.arange(N, device=self.device).repeat_interleave(B)
-        obs, act, rew = s["obs"].reshape(N * B, -1), s["action"].reshape(-1), s["reward"].reshape(-1)
-        nobs, done, rep = s["next_obs"].reshape(N * B, -1), s["done"].reshape(-1), s["replica"].reshape(-1)
-        w = s["weights"].reshape(N, B).to(torch.float32)
-        with torch.no_grad():
-            # "target" signalling: the buffer holds the targets the next nodes computed
-            tgt = rew if self.signaling == "target" else self.targets(node, act, rew, nobs, done, rep)
+        if engine is not None:
+            idx = self.buffers.sample_idx(B, self.gen)
+            w = self.buffers.importance_weights(idx).reshape(N, B).to(torch.float32)
+            weights, gen_of = self._device_generations()
+            out = engine.replay_targets(self.buffers, idx, weights, self.kind, self.gamma, gen_of)
+            obs, act, tgt = out["obs"], out["action"], out["target"]
+            self.last_batch = {"idx": idx, "target": tgt, "status": out["status"], "gen_of": gen_of,
+                               "weights": weights}
+        else:
+            s = self.buffers.sample_full(B, self.gen)
+            obs, act, rew = s["obs"].reshape(N * B, -1), s["action"].reshape(-1), s["reward"].reshape(-1)
+            nobs, done, rep = s["next_obs"].reshape(N * B, -1), s["done"].reshape(-1), s["replica"].reshape(-1)
+            w = s["weights"].reshape(N, B).to(torch.float32)
+            with torch.no_grad():
+                # "target" signalling: the buffer holds the targets the next nodes computed
+                tgt = rew if self.signaling == "target" else self.targets(node, act, rew, nobs, done, rep)
         q = self.q.q_values(obs, node)
         qsel = q.gather(1, act[:, None]).squeeze(1)
         per = (w * huber(qsel - tgt).view(N, B)).mean(dim=1)          # learner.py:179, per node
@@ -841,6 +919,8 @@ class QRoutingTrainer:
                 "stored_bytes": len(self._gen_w) * self.generation_bytes,
                 "peak_generations": int(self.peak_generations),
                 "peak_stored_bytes": int(self.peak_generations) * self.generation_bytes,
+                # the packed device copies train_step(engine=) keeps of the stored generations
+                "packed_generation_bytes": sum(t.numel() * t.element_size() for t in self._gen_packed.values()),
                 # every count of the smart-exploration history (R * T ones + the decisions counted), 0 without
                 "action_history_total": (int((self.action_history.long() & 0xFFFFFFFF).sum())
                                          if self.action_history is not None else 0)}
@@ -862,9 +942,12 @@ class QRoutingTrainer:
         used = set(self._snap_gen.values())
         for g in [g for g in self._gen_w if g not in used]:
             del self._gen_w[g]
+        for g in [g for g in self._gen_packed if g not in self._gen_w]:
+            del self._gen_packed[g]
 
 
-def train(env, trainer: QRoutingTrainer, steps: int, train_every: int = 1, sync_every: Optional[int] = None):
+def train(env, trainer: QRoutingTrainer, steps: int, train_every: int = 1, sync_every: Optional[int] = None,
+          fused_targets: bool = False):
     """Drive a VecRoutingEnv (external-action mode) with the trainer's epsilon-greedy
     policy: each step applies one action per replica, hands the step's notifications and
     completed transitions to the trainer (on_step: clocks, buffers, signalling, syncs), and
@@ -872,7 +955,13 @@ def train(env, trainer: QRoutingTrainer, steps: int, train_every: int = 1, sync_
 
     ``sync_every`` (syncs every k env steps) is gone: syncs follow each replica's simulated
     clock and ``QRoutingTrainer(sync_step=...)`` (trainer.py:101-112). Passing it warns and
-    is otherwise ignored."""
+    is otherwise ignored.
+
+    ``fused_targets=True`` takes every training step's batch and targets from one device pass
+    (train_step(engine=env.engine), prisma_replay_targets); ``signaling_type="target"`` keeps its
+    targets in the buffer: ValueError before the env is used."""
+    if fused_targets:
+        trainer._check_fused_targets()
     if sync_every is not None:
         warnings.warn("train(sync_every=...) is ignored: syncs follow the replicas' simulated clocks; set "
                       "QRoutingTrainer(sync_step=seconds) instead", DeprecationWarning, stacklevel=2)
@@ -884,14 +973,14 @@ def train(env, trainer: QRoutingTrainer, steps: int, train_every: int = 1, sync_
         obs, _, _, info = env.step(a)
         trainer.on_step(obs, info)
         if s % train_every == 0:
-            per = trainer.train_step()
+            per = trainer.train_step(engine=env.engine if fused_targets else None)
             if per is not None:
                 losses.append(float(torch.nanmean(per)))
     return losses
 
 
 def train_fused(env, trainer: QRoutingTrainer, launches: int, hops_per_launch: int, train_every: int = 1,
-                fused_ingest: bool = False):
+                fused_ingest: bool = False, fused_targets: bool = False):
     """Train from in-kernel rollouts: every launch is a fused epsilon-greedy run of up to
     ``hops_per_launch`` hops per replica (VecRoutingEnv.run(..., explore=...), the exploring step
     kernels) instead of one decision per replica per launch as in train().  Per launch: the fused
@@ -910,12 +999,19 @@ def train_fused(env, trainer: QRoutingTrainer, launches: int, hops_per_launch: i
     (prisma_ingest_transitions), bit-identical to the default observe(env.transitions()) and
     without its host reads; non-prioritized buffers only (ValueError before the env is used).
 
+    ``fused_targets=True`` takes every training step's batch and targets from one device pass
+    (train_step(engine=env.engine), prisma_replay_targets: the sampled rows gathered from the rings
+    and every stored generation evaluated in one launch, no host read); ``signaling_type="target"``
+    keeps its targets in the buffer: ValueError before the env is used.
+
     "ideal" signalling only (a transition enters the buffer when it completes; the others wait for
     signalling packets the fused rollout does not hand out).  A launch that writes more records
     than the env's log ring holds would lose transitions silently: RuntimeError; size
     ``log_capacity`` above the decisions a launch makes (hops plus destination arrivals).  A replica
     the engine stopped on a PRISMA_EBIT_* failure produces nothing more: RuntimeError naming the
     bits and the number of replicas."""
+    if fused_targets:
+        trainer._check_fused_targets()
     if trainer.signaling != "ideal":
         raise ValueError("train_fused needs signaling_type='ideal' (hop transitions of 'NN' / 'target' wait for "
                          "signalling packets): use train()")
@@ -956,7 +1052,7 @@ def train_fused(env, trainer: QRoutingTrainer, launches: int, hops_per_launch: i
             trainer.observe(env.transitions())
         trainer.check_sync()
         if k % train_every == 0:
-            per = trainer.train_step()
+            per = trainer.train_step(engine=env.engine if fused_targets else None)
             if per is not None:
                 losses.append(float(torch.nanmean(per)))
     return losses

@@ -14,8 +14,14 @@
      env.ingest_transitions(buffers) (prisma_ingest_transitions) on the same log, wall time and peak
      allocated memory of each, and train_fused() with fused_ingest off and on, transitions/s; run it
      with --hops 256 and --hops 8192
+  f  the targets of a training step, for --kinds routing,buffer: (i) QRoutingTrainer.targets() alone and
+     train_step() on the torch path, with one stored generation, with the generations a
+     --gen-steps train() run leaves and with --forced-gens made-up ones (replica r reading
+     generation r mod G, the state of a long run); (ii) PrismaEngine.replay_targets
+     (prisma_replay_targets) and train_step(engine=) on the same batch; (iii) train_fused()
+     iterations at --hops-list hops with fused_targets off and on
 
-    python scripts/rollout_bench.py --part a        # or b, c, d, e; --repeat 2 prints each line twice
+    python scripts/rollout_bench.py --part a        # or b, c, d, e, f; --repeat 2 prints each line twice
 
 Every part warms up first and is timed between device synchronisations.  bench.py stays the
 headline's yardstick; this script only compares the rollout paths with each other."""
@@ -42,10 +48,10 @@ def pow2_at_least(n: int) -> int:
     return p
 
 
-def make(args, log_capacity):
+def make(args, log_capacity, kind="routing"):
     env = VecRoutingEnv(args.topology, n_replicas=args.replicas, sim_time_s=60.0, auto_reset=1,
                         log_capacity=log_capacity)
-    tr = QRoutingTrainer(env.topo, "routing", n_replicas=args.replicas, seed=0, batch_size=args.batch,
+    tr = QRoutingTrainer(env.topo, kind, n_replicas=args.replicas, seed=0, batch_size=args.batch,
                          eps_initial=args.eps, eps_final=args.eps)
     return env, tr
 
@@ -212,9 +218,103 @@ def part_e(args):
     env.close()
 
 
+def part_f(args):
+    import statistics
+
+    def med(fn, n=args.timed):
+        fn()                                                  # (warm: allocator, first-call tables)
+        return statistics.median(wall(fn)[0] for _ in range(n))
+
+    for kind in args.kinds.split(","):
+        # (i), (ii): the targets of one sampled batch, torch path against prisma_replay_targets
+        env, tr = make(args, 8192, kind)
+        train_fused(env, tr, 4, 256, fused_ingest=True)       # fills the rings past the batch size
+        N, B = tr.N, tr.batch_size
+        node = torch.arange(N, device=tr.device).repeat_interleave(B)
+        for stage in ("one generation", f"after a {args.gen_steps}-step train()",
+                      f"{args.forced_gens} generations, replicas assigned in turn"):
+            if stage == "one generation":
+                tr.sync()
+                tr.sync()                                     # every copy refers to the newest generation
+            elif stage.startswith("after"):
+                train(env, tr, args.gen_steps)
+            else:
+                # what a long run's drifting replica clocks leave (29 at the
+                # peak), made here: a new version of perturbed weights per step, read by every G-th replica
+                for g in range(args.forced_gens):
+                    with torch.no_grad():
+                        for p in tr.params:
+                            p.mul_(1.0 + 1e-3 * (g + 1))
+                    tr.version += 1
+                    tr._snap_gen[tr.version] = tr._capture()
+                    tr.tgt_ver[g::args.forced_gens] = tr.version
+            gens = len({tr._snap_gen[int(k)] for k in set(tr.tgt_ver.ravel().tolist())})
+            idx = tr.buffers.sample_idx(B, tr.gen)
+
+            def torch_targets():
+                s = tr.buffers.sample_full(B, idx=idx)
+                with torch.no_grad():
+                    return tr.targets(node, s["action"].reshape(-1), s["reward"].reshape(-1),
+                                      s["next_obs"].reshape(N * B, -1), s["done"].reshape(-1), s["replica"].reshape(-1))
+
+            def only_targets(s):
+                with torch.no_grad():
+                    return tr.targets(node, s["action"].reshape(-1), s["reward"].reshape(-1),
+                                      s["next_obs"].reshape(N * B, -1), s["done"].reshape(-1), s["replica"].reshape(-1))
+
+            s0 = tr.buffers.sample_full(B, idx=idx)
+            weights, gen_of = tr._device_generations()
+            ref = torch_targets()
+            out = env.engine.replay_targets(tr.buffers, idx, weights, kind, tr.gamma, gen_of)
+            fin = torch.isfinite(ref)
+            err = float(((out["target"] - ref).abs() / ref.abs().clamp_min(1.0))[fin].max()) if bool(fin.any()) else 0.0
+            t_targets = med(lambda: only_targets(s0))
+            t_sample_targets = med(torch_targets)
+            t_kernel = med(lambda: env.engine.replay_targets(tr.buffers, idx, weights, kind, tr.gamma, gen_of))
+            # (the training steps last: they move the online weights, not the stored generations)
+            t_step = med(lambda: tr.train_step())
+            t_step_fused = med(lambda: tr.train_step(engine=env.engine))
+            line = common(args, "f")
+            line.update(agent=kind, path="targets of one batch: torch targets() vs prisma_replay_targets", stage=stage,
+                        live_generations=gens, stored_generations=len(tr._gen_w), rows=N * B,
+                        torch_targets_s=round(t_targets, 6), torch_sample_and_targets_s=round(t_sample_targets, 6),
+                        replay_targets_s=round(t_kernel, 6), torch_over_kernel=round(t_sample_targets / t_kernel, 2),
+                        train_step_torch_s=round(t_step, 6), train_step_fused_targets_s=round(t_step_fused, 6),
+                        max_rel_diff_finite=err, timed=args.timed)
+            print(json.dumps(line), flush=True)
+        env.close()
+        del env, tr
+        torch.cuda.empty_cache()
+        # (iii) train_fused iterations with and without fused_targets
+        for hops in [int(h) for h in args.hops_list.split(",")]:
+            env, tr = make(args, pow2_at_least(2 * hops), kind)
+            train_fused(env, tr, args.warmup_launches, hops, fused_ingest=True, fused_targets=True)
+            for _ in range(args.repeat):
+                res = {}
+                for name, fused in (("torch", False), ("kernel", True)):
+                    dt, losses = wall(lambda: train_fused(env, tr, args.launches, hops, fused_ingest=True,
+                                                          fused_targets=fused))
+                    res[name] = (dt / args.launches, len(losses))
+                line = common(args, "f")
+                line.update(agent=kind, path="train_fused iteration: targets() vs fused_targets", hops_per_launch=hops,
+                            log_capacity=env.engine.log_capacity, launches=args.launches,
+                            stored_generations=len(tr._gen_w),
+                            iteration_torch_targets_ms=round(1e3 * res["torch"][0], 3),
+                            iteration_fused_targets_ms=round(1e3 * res["kernel"][0], 3), train_steps=res["kernel"][1])
+                print(json.dumps(line), flush=True)
+            env.close()
+            del env, tr
+            torch.cuda.empty_cache()
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument("--part", choices=["a", "b", "c", "d", "e"], required=True)
+    p.add_argument("--part", choices=["a", "b", "c", "d", "e", "f"], required=True)
+    p.add_argument("--kinds", default="routing,buffer", help="agent kinds (part f)")
+    p.add_argument("--hops-list", default="256,8192", help="hops per launch of the train_fused iterations (part f)")
+    p.add_argument("--gen-steps", type=int, default=600, help="train() steps that spread the generations (part f)")
+    p.add_argument("--forced-gens", type=int, default=29, help="generations of the made-up spread (part f)")
+    p.add_argument("--timed", type=int, default=7, help="timed calls per figure, the median is reported (part f)")
     p.add_argument("--topology", default="abilene")
     p.add_argument("--replicas", type=int, default=4096)
     p.add_argument("--eps", type=float, default=0.1)
@@ -226,7 +326,7 @@ def main(argv=None):
     p.add_argument("--warmup-steps", type=int, default=20)
     p.add_argument("--repeat", type=int, default=2, help="timed repeats, one JSON line each (the spread)")
     args = p.parse_args(argv)
-    {"a": part_a, "b": part_b, "c": part_c, "d": part_d, "e": part_e}[args.part](args)
+    {"a": part_a, "b": part_b, "c": part_c, "d": part_d, "e": part_e, "f": part_f}[args.part](args)
 
 
 if __name__ == "__main__":
