@@ -222,12 +222,14 @@ def first_difference(got, ref):
                 min(len(got), len(ref)))
 
 
-def run_fused_both(oracle_mod, topo, params, R, H, policy, *, launches=1, kernel=None, net_cpu=None, label=""):
+def run_fused_both(oracle_mod, topo, params, R, H, policy, *, launches=1, kernel=None, net_cpu=None, label="",
+                   kernel_name=None):
     """R replicas x H hops of a fused policy, ("table", uint8 [N, N]) or ("mlp", packed fp32 numpy),
     in `launches` launches on the engine and in one run on the oracle: every record and the
     counters of every replica byte for byte, as test_gpu_parity.run_table_both.  kernel: the
-    prisma_kernel_info fields the engine must report.  net_cpu: the torch model of an MLP policy,
-    for check_near_ties.  Returns (counters, per-replica oracle records)."""
+    prisma_kernel_info fields the engine must report; kernel_name: what the name of the instance
+    the run launches must start with.  net_cpu: the torch model of an MLP policy, for
+    check_near_ties.  Returns (counters, per-replica oracle records)."""
     import torch
     from prisma_amd.engine import PrismaEngine
     kind, pol = policy
@@ -236,6 +238,9 @@ def run_fused_both(oracle_mod, topo, params, R, H, policy, *, launches=1, kernel
         if kernel is not None:
             ki = eng.kernel_info()
             assert {k: ki[k] for k in kernel} == kernel, (label, ki)
+        if kernel_name is not None:
+            name = eng.kernel_name if kind == "table" else eng.kernel_name_mlp
+            assert name.startswith(kernel_name), (label, name)
         eng.reset(0)
         dev = torch.from_numpy(np.ascontiguousarray(pol)).cuda()
         for _ in range(launches):
