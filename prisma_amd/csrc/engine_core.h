@@ -343,7 +343,8 @@ struct Sim {
     bool lanel;                             // lane-resident link handlers (lane_links_bind; constant)
     // ... and their per-lane constants of link `lane`: ring offset | capacity << 16, tx time of a
     // data / ping entry and the propagation delay (low 32 bits), the admission limit (bytes on a
-    // switch link, packets on an access link) and the access-link mask (all ones / 0)
+    // switch link, packets on an access link) and the topology word (access flag on top, the far
+    // end, its row pointer and degree below: lane_links_bind)
     uint32_t lk_rinfo, lk_txd, lk_txp, lk_prop, lk_lim, lk_acc;
     // memory-resident engine: variable-size topology arrays (scalar loads)
     const CAS int32_t* m_rowptr;
@@ -848,6 +849,22 @@ __device__ __forceinline__ bool ring_store_needed(const Sim& S, const LinkV& k) 
 #ifndef PRISMA_LANE_LINKS
 #define PRISMA_LANE_LINKS 7
 #endif
+// PRISMA_FLAT_SEND (build switch for the A/B variants of profiles/flat_sends/): link_send_lane
+// commits with per-lane predicates and no uniform branch on the status word -- 1 fully flat, 2 flat
+// behind the uniform early exit of a dropped send (the default: the headline's random-initialised
+// table drops often, and the fully flat form lost 1.5 % there), 0 the branching form.
+// PRISMA_TOPO_WORD: lk_acc carries the link's far end and that node's row (lane_links_bind), which
+// a data arrival takes from one v_readlane instead of three dependent scalar loads.
+#ifndef PRISMA_FLAT_SEND
+#define PRISMA_FLAT_SEND 2
+#endif
+#ifndef PRISMA_TOPO_WORD
+#define PRISMA_TOPO_WORD 1
+#endif
+// the access mask (all ones / 0) of lane_links_bind's lk_acc
+__device__ __forceinline__ uint32_t lk_acc_mask(uint32_t acc) {
+    return PRISMA_TOPO_WORD ? (uint32_t)((int32_t)acc >> 31) : acc;
+}
 __device__ __forceinline__ void lane_links_bind(Sim& S) {
     const LV& L = S.lv;
     const uint32_t l = (uint32_t)S.lane;         // (the image's arrays hold 256 links, zero past L)
@@ -857,7 +874,19 @@ __device__ __forceinline__ void lane_links_bind(Sim& S) {
     S.lk_txp = S.T->ltx[2u * (l * 8u + T_PFWD)];
     S.lk_prop = S.T->ltx[2u * (l * 8u + T_RELAY) + 1u] - S.lk_txd;
     S.lk_lim = acc ? L.acc_qmax_pkts() : L.qmax_bytes();
-    S.lk_acc = acc ? ~0u : 0u;
+    if (PRISMA_TOPO_WORD) {
+        // the link's topology word: far end v (bits 0-7), v's row pointer (8-15) and degree
+        // (16-23), the access flag on top.  8 bits hold whatever the image can: its arrays end at
+        // 256 links, nodes and tunnels (an LS = 1 instance meets at most 64 links, so 33 nodes,
+        // row pointers up to 63 and degrees up to 21)
+        static_assert(sizeof(TopoImage::ldst) / sizeof(int32_t) <= 256 && sizeof(TopoImage::ovrow) / sizeof(int32_t) <= 256 &&
+                      sizeof(TopoImage::tinfo) / sizeof(uint32_t) <= 256, "topology word: 8-bit fields");
+        const uint32_t v = (uint32_t)S.T->ldst[l];
+        const uint32_t r0 = (uint32_t)S.T->ovrow[v], deg = (uint32_t)S.T->ovrow[v + 1u] - r0;
+        S.lk_acc = (acc ? 1u << 31 : 0u) | (deg & 255u) << 16 | (r0 & 255u) << 8 | (v & 255u);
+    } else {
+        S.lk_acc = acc ? ~0u : 0u;
+    }
     asm volatile("" : "+v"(S.lk_rinfo), "+v"(S.lk_txd), "+v"(S.lk_txp), "+v"(S.lk_prop), "+v"(S.lk_lim),
                  "+v"(S.lk_acc));
 }
@@ -878,7 +907,8 @@ __device__ __forceinline__ int link_send_lane(const Sim& S, Regs<FS, LS>& R, Hot
     const uint32_t nq = p2 & 0xffffu, nw = p1 >> 16, tail = p1 & 0xffffu;
     const uint32_t off = S.lk_rinfo & 0xffffu, cap = S.lk_rinfo >> 16;
     // admission: queued bytes on a switch link, queued packets on an access link
-    const uint32_t have = (S.lk_acc & (nq + 1u)) | (~S.lk_acc & (qb + size));
+    const uint32_t am = lk_acc_mask(S.lk_acc);
+    const uint32_t have = (am & (nq + 1u)) | (~am & (qb + size));
     const bool drop = have > S.lk_lim;
     // an elided completion that precedes the event being executed has happened (lazy_due)
     const uint64_t dd = ((uint64_t)(R.cp_t.v[0] - lo32(H.now)) << 32) + (uint64_t)R.cp_seq.v[0] - (uint64_t)H.cur_seq;
@@ -892,6 +922,46 @@ __device__ __forceinline__ int link_send_lane(const Sim& S, Regs<FS, LS>& R, Hot
     st |= (start && nw + 1u > WC) ? LST_WIRE : 0u;
     st |= (start && nq != 0u) ? LST_OLDER : 0u;
     const uint32_t s = rdl(st, l);
+    if constexpr (PRISMA_FLAT_SEND != 0) {
+        // One straight-line body: the owner lane commits under its own predicates and the scalar
+        // side takes the sequence numbers, the event count and the flags from the status word.
+        // (With uniform branches on the word the START and the queue path wrote different subsets
+        // of the lane fields, which the compiler copied out and back around every inlined site.)
+        // A dropped send changes nothing (no other bit stands beside LST_DROP); a ring failure
+        // changes nothing but ev_launch (if due) and the flags; a wire failure sets its flag after
+        // the state update.
+        if (PRISMA_FLAT_SEND == 2 && (s & LST_DROP)) return 0;
+        const bool ok = me && !drop && !rfail;
+        const bool go = ok && start;
+        const uint32_t xi = p0 >> 16;
+        uint32_t hx = e;
+        if (go && nq != 0u) hx = S.ring[off + xi];                     // (a queue behind an idle transmitter)
+        const uint32_t nt = (tail + 1u == cap) ? 0u : tail + 1u;
+        const uint32_t nx = (xi + 1u == cap) ? 0u : xi + 1u;
+        const bool ping = (hx & 2u) != 0u;
+        const uint32_t cpt = lo32(H.now) + (ping ? S.lk_txp : S.lk_txd);
+        const uint32_t at = cpt + S.lk_prop;
+        const uint32_t cps = H.seq, as = H.seq + 1u;                   // TransmitComplete, channel Receive
+        H.seq += (s / LST_START) * 2u & 2u;
+        H.ev_launch += (s / LST_DUE) & 1u;
+        if (ok) S.ring[off + tail] = e;
+        if (go) {
+            S.wt[l * WC + (xi & (WC - 1u))] = at;
+            S.wseq[l * WC + (xi & (WC - 1u))] = as;
+        }
+        R.p0.v[0] = go ? ((p0 & 0xffffu) | (nx << 16)) : p0;
+        R.p1.v[0] = ok ? (nt | ((nw + (start ? 1u : 0u)) << 16)) : p1;
+        R.p2.v[0] = ok ? (start ? (nq | 0x10000u) : p2 + 1u) : p2;
+        R.qb.v[0] = ok ? qb + size - (start ? (ping ? psz : dsz) : 0u) : qb;
+        R.cp_t.v[0] = go ? cpt : R.cp_t.v[0];
+        R.cp_seq.v[0] = go ? cps : R.cp_seq.v[0];
+        const bool head = go && nw == 0u;                              // the wire was empty: new head
+        R.wh_t.v[0] = head ? at : R.wh_t.v[0];
+        R.wh_seq.v[0] = head ? as : R.wh_seq.v[0];
+        if (__builtin_expect((s & (LST_RING | LST_WIRE)) != 0u, 0))
+            fail(H, (s & LST_RING) ? PRISMA_EBIT_RING : PRISMA_EBIT_WIRE);
+        return (s & (LST_DROP | LST_RING)) == 0u;
+    }
     if (s & LST_DROP) return 0;
     H.ev_launch += (s / LST_DUE) & 1u;
     if (s & LST_RING) { fail(H, PRISMA_EBIT_RING); return 0; }
@@ -2388,12 +2458,18 @@ __device__ __forceinline__ int on_arrive(const Sim& S, RS& R, Hot& H, uint32_t l
     const LV& L = S.lv;
     if (S.mem) TP1_START();
     TP2_START();
-    const uint32_t v = (uint32_t)t_ldst(S, l);
+    // lane-resident link handlers: the far end, its row and the ring offset are constants of link
+    // l held in its lane (lane_links_bind), one v_readlane each instead of a scalar load and two
+    // dependent on it
+    bool topo_word = false;
+    if constexpr (!RS::kMem && PRISMA_TOPO_WORD != 0) topo_word = S.lanel;
+    const uint32_t tw = topo_word ? rdl(S.lk_acc, l) : 0u;
+    const uint32_t v = topo_word ? (tw & 255u) : (uint32_t)t_ldst(S, l);
     LinkV k = link_get(R, l);
     const uint32_t wh = k.head & (uint32_t)(L.WCAP() - 1);
     const uint32_t x = S.mem ? wire_ent(S, k, wh)
                              : (S.tun ? u_ld32(&S.went[l * (uint32_t)L.WCAP() + wh])
-                                      : u_ld32(&S.ring[ring_off(S, l) + k.head]));
+                                      : u_ld32(&S.ring[(topo_word ? rdl(S.lk_rinfo, l) & 0xffffu : ring_off(S, l)) + k.head]));
     if (S.mem) TP1(0);
     TP2(0);
     const uint32_t type = ent_type(x);
@@ -2495,7 +2571,8 @@ __device__ __forceinline__ int on_arrive(const Sim& S, RS& R, Hot& H, uint32_t l
         }
         H.dec = d + 1u;
         int r0 = -1, deg = 0;
-        if (!S.mem) { r0 = t_ovrow(S, v); deg = t_ovrow(S, v + 1) - r0; }
+        if (topo_word) { r0 = (int)((tw >> 8) & 255u); deg = (int)((tw >> 16) & 255u); }
+        else if (!S.mem) { r0 = t_ovrow(S, v); deg = t_ovrow(S, v + 1) - r0; }
         const uint32_t obs_links = S.mem ? obs_early : observe_links(S, R, H, v, ns_to_sec(H.now), r0, deg);
         D.r0 = r0; D.deg = deg;
         int64_t t_prev = 0;
