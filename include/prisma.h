@@ -712,6 +712,92 @@ typedef struct prisma_plan {
 } prisma_plan_t;
 int prisma_plan(const prisma_topology_t* topo, const prisma_params_t* params, prisma_plan_t* out);
 
+/*
+ * Traffic scenarios: replicas of one env that differ in their flow rates (traffic matrix, load
+ * factor), advanced by the same launches.  The flow LIST (n_flows, flow_src, flow_dst) and the rest
+ * of the topology are those of `topo` for every scenario; scenario s gives flow f the bit rate
+ * flow_rate_bps[s * n_flows + f], and replica r (local index, 0 .. n_replicas - 1) runs scenario
+ * scenario_of[r].  Everything else of a replica -- its Philox key (seed, replica_base + r), its
+ * ns-3 streams, sizing, kernels -- is what prisma_create gives it, so replica r equals the replica
+ * with the same global id of a single-scenario env on scenario_of[r]'s rates.
+ *
+ * With a scenario set the rates come from it: topo->flow_rate_bps is not read, but must still be
+ * non-null, as prisma_create requires.  prisma_create(topo, ...) IS prisma_create_scenarios with
+ * n_scenarios = 1, row 0 = topo->flow_rate_bps and every replica in scenario 0 (one code path:
+ * state, log and counters are byte-identical either way).
+ *
+ * The device holds one read-only topology image per scenario, back to back, and a replica binds
+ * its scenario's image by a 32-bit byte offset: n_scenarios <= PRISMA_MAX_SCENARIOS and
+ * n_scenarios * (image bytes rounded up to 256) < 2^32 (prisma_scenario_plan_t.topo_bytes), else
+ * PRISMA_ERR_CONFIG.
+ *
+ * PRISMA_ERR_ARG: a null scenarios / flow_rate_bps / scenario_of, n_scenarios < 1 (and what
+ * prisma_create refuses); PRISMA_ERR_CONFIG: a zero rate, a scenario_of entry outside
+ * [0, n_scenarios), too many scenarios.  The message names the argument.  Both arrays are host
+ * memory, copied by the call.  (Added without an ABI version change: no struct or signature moved.)
+ */
+#define PRISMA_MAX_SCENARIOS 65535
+typedef struct prisma_scenarios {
+    int32_t n_scenarios;            /* S >= 1 */
+    const uint64_t* flow_rate_bps;  /* [S][topo->n_flows], every entry > 0 */
+    const int32_t*  scenario_of;    /* [n_replicas], each in [0, S); local replica index */
+} prisma_scenarios_t;
+
+int prisma_create_scenarios(const prisma_topology_t* topo, const prisma_params_t* params,
+                            const prisma_scenarios_t* scenarios, int32_t n_replicas, int32_t device,
+                            prisma_env_t** out);
+
+/* prisma_plan for a scenario set: the same validation as prisma_create_scenarios, no device; `out`
+ * reports what prisma_plan does (the per-replica footprint does not depend on the rates). */
+int prisma_plan_scenarios(const prisma_topology_t* topo, const prisma_params_t* params,
+                          const prisma_scenarios_t* scenarios, int32_t n_replicas, prisma_plan_t* out);
+
+/* ... and the read-only topology images of the set, which prisma_plan_t has no room for
+ * (its size is fixed): the same validation once more. */
+typedef struct prisma_scenario_plan {
+    uint64_t topo_bytes;        /* device bytes of all scenarios' topology images */
+    uint32_t image_bytes;       /* one image                                       */
+    int32_t  n_scenarios;
+} prisma_scenario_plan_t;
+int prisma_plan_scenario_images(const prisma_topology_t* topo, const prisma_params_t* params,
+                                const prisma_scenarios_t* scenarios, int32_t n_replicas,
+                                prisma_scenario_plan_t* out);
+
+/* The env's scenario count and (scenario_of_out non-null: host int32 [n_replicas]) each replica's
+ * scenario; 1 and zeros for an env made by prisma_create.  Either pointer may be NULL. */
+int prisma_scenario_info(prisma_env_t* env, int32_t* n_scenarios, int32_t* scenario_of_out);
+
+/*
+ * Per-scenario sums of the replicas' counters: one launch on `stream`, no host read.  out_device:
+ * device prisma_scenario_stats_t [n_scenarios].  One wavefront per scenario walks that scenario's
+ * replicas in ascending replica index (a host-built CSR that prisma_create / prisma_create_scenarios
+ * put on the device, so the call itself allocates and copies nothing).
+ *
+ * Integer fields are exact sums (uint64 / int64; the 32-bit counters widened first).  n_error counts
+ * the replicas with error != 0, n_over those with episode_over != 0.
+ *
+ * The f64 sums are in a fixed order, independent of the launch shape, so a host can restate them
+ * bit for bit (prisma_amd/scenarios.py stats_sum): with x_0 .. x_{n-1} the scenario's values in
+ * ascending replica index (the float counters converted to double, which is exact),
+ *     lane l (0 <= l < 64):  a_l = +0.0;  for p = l, l + 64, l + 128, ... < n:  a_l = a_l + x_p
+ *     for h = 32, 16, 8, 4, 2, 1:  for l < h:  a_l = a_l + a_{l + h}       (all l of a level at once)
+ *     sum = a_0
+ * every addition an IEEE-754 binary64 round-to-nearest-even add, none fused or reassociated.
+ */
+typedef struct prisma_scenario_stats {
+    uint64_t n_replicas;        /* replicas of the scenario                 */
+    uint64_t n_error;           /* ... with error != 0                      */
+    uint64_t n_over;            /* ... with episode_over != 0               */
+    uint64_t events, hops, decisions, hop_deg_sum;
+    int64_t  now_ns;
+    int64_t  ov_injected, ov_arrived, ov_lost, un_injected, un_arrived, un_lost;
+    int64_t  bytes_data, bytes_signaling, cost_n, e2e_n, un_cost_n;
+    uint64_t episode, ping_rounds, seq, uid, dec_count, ctrl_dropped;
+    uint64_t hops_total, events_total;
+    double   reward_sum, cost_sum, e2e_sum, un_cost_sum;
+} prisma_scenario_stats_t;
+int prisma_scenario_stats(prisma_env_t* env, prisma_scenario_stats_t* out_device, void* stream);
+
 void prisma_destroy(prisma_env_t* env);
 
 #ifdef __cplusplus

@@ -112,7 +112,20 @@ struct KParams {
                                  // null; T = ovrow[N].  Last again: no other instance's kernarg offset moves
     const uint32_t* stoch_tab;   // [NO][NO][T] class << 24 | weight (prisma_run_stochastic, the stoch instances), or
                                  // null; last once more
+    const uint32_t* topo_off;    // [R] byte offset of replica r's topology image in `topo` (an env with a scenario
+                                 // set: one whole image per scenario, prisma_create_scenarios), or null: every
+                                 // replica reads the image at `topo`.  Last, as the others
 };
+
+// The topology image replica r binds: one scalar load at the start of a launch, and with a single
+// scenario (null) the pointer every kernel took before.  The event loop sees one base pointer
+// either way (Sim::T, the memory-resident engine's m_* arrays).
+__device__ __forceinline__ const unsigned char* replica_topo(const KParams& P, int r) {
+    // (the offset selected as a 32-bit value and added once: selecting between the two 64-bit pointers
+    // instead cost the headline 0.7 % in alternating A/B, with the same register counts)
+    const uint32_t off = P.topo_off ? P.topo_off[r] : 0u;
+    return P.topo + off;
+}
 
 // ---------------------------------------------------------------------------
 // cross-lane helpers

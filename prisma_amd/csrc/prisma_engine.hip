@@ -68,7 +68,7 @@ __global__ void __launch_bounds__(64) prisma_reset_kernel_t(KParams P) {
     LV lv;
     lv.load(P.lay, lane);
     Sim S;
-    sim_bind(S, lv, lds, P.topo, P.log + (size_t)r * LC.log_cap * LC.rec_bytes, LC.replica_base + (uint32_t)r, lane);
+    sim_bind(S, lv, lds, replica_topo(P, r), P.log + (size_t)r * LC.log_cap * LC.rec_bytes, LC.replica_base + (uint32_t)r, lane);
     Hot H;
     memset(&H, 0, sizeof(H));
     const bool keep = (P.mode == 3);
@@ -194,6 +194,66 @@ __global__ void __launch_bounds__(kCompactThreads) prisma_expand_kernel(
         const int32_t r = ids[i];
         if ((uint32_t)r < (uint32_t)R) actions[r] = packed[i];
     }
+}
+
+// Per-scenario sums of the replicas' counters (prisma_scenario_stats; the order rule is in
+// include/prisma.h): one wave per scenario; lane l takes positions l, l + 64, ... of the scenario's
+// replica list in turn, then the 64 lane sums fold in halves, 32 down to 1.  The doubles are added
+// one IEEE add at a time in exactly that order (the build has no fast-math and no contraction), so
+// a host restates them bit for bit; the integer sums are exact in any order.
+__device__ __forceinline__ double stats_fold(double a) {
+    for (int h = 32; h >= 1; h >>= 1) a = a + __shfl_down(a, h, kWave);   // (lanes >= h: unused)
+    return a;
+}
+__device__ __forceinline__ uint64_t stats_fold(uint64_t a) {
+    for (int h = 32; h >= 1; h >>= 1) a = a + (uint64_t)__shfl_down((unsigned long long)a, h, kWave);
+    return a;
+}
+__global__ void __launch_bounds__(64) prisma_scenario_stats_kernel(
+        const prisma_counters_t* __restrict__ cnt, const int32_t* __restrict__ row, const int32_t* __restrict__ ids,
+        int32_t R, prisma_scenario_stats_t* __restrict__ out) {
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const int32_t lo = row[s], hi = row[s + 1];
+    // the integer fields in the order of prisma_scenario_stats_t after n_replicas (two's complement:
+    // the signed ones sum as uint64 too), then the four doubles
+    constexpr int kInts = 26;
+    uint64_t a[kInts];
+    double d[4] = { 0.0, 0.0, 0.0, 0.0 };
+    for (int k = 0; k < kInts; ++k) a[k] = 0;
+    for (int32_t p = lo + lane; p < hi; p += kWave) {
+        const int32_t r = ids[p];
+        if ((uint32_t)r >= (uint32_t)R) continue;        // (the host builds none)
+        const prisma_counters_t c = cnt[r];
+        int k = 0;
+        a[k++] += c.error != 0u;
+        a[k++] += c.episode_over != 0u;
+        a[k++] += c.events; a[k++] += c.hops; a[k++] += c.decisions; a[k++] += c.hop_deg_sum;
+        a[k++] += (uint64_t)c.now_ns;
+        a[k++] += (uint64_t)(int64_t)c.ov_injected; a[k++] += (uint64_t)(int64_t)c.ov_arrived;
+        a[k++] += (uint64_t)(int64_t)c.ov_lost; a[k++] += (uint64_t)(int64_t)c.un_injected;
+        a[k++] += (uint64_t)(int64_t)c.un_arrived; a[k++] += (uint64_t)(int64_t)c.un_lost;
+        a[k++] += (uint64_t)(int64_t)c.bytes_data; a[k++] += (uint64_t)(int64_t)c.bytes_signaling;
+        a[k++] += (uint64_t)(int64_t)c.cost_n; a[k++] += (uint64_t)(int64_t)c.e2e_n;
+        a[k++] += (uint64_t)(int64_t)c.un_cost_n;
+        a[k++] += c.episode; a[k++] += c.ping_rounds; a[k++] += c.seq; a[k++] += c.uid; a[k++] += c.dec_count;
+        a[k++] += c.ctrl_dropped;
+        a[k++] += c.hops_total; a[k++] += c.events_total;
+        d[0] = d[0] + c.reward_sum;
+        d[1] = d[1] + (double)c.cost_sum;
+        d[2] = d[2] + (double)c.e2e_sum;
+        d[3] = d[3] + (double)c.un_cost_sum;
+    }
+    uint64_t* o = (uint64_t*)(out + s);
+    static_assert(sizeof(prisma_scenario_stats_t) == 8 * (1 + 26 + 4), "prisma_scenario_stats_t: 31 eight-byte fields");
+    for (int k = 0; k < 26; ++k) {
+        const uint64_t v = stats_fold(a[k]);
+        if (lane == 0) o[1 + k] = v;
+    }
+    for (int k = 0; k < 4; ++k) {
+        const double v = stats_fold(d[k]);
+        if (lane == 0) ((double*)o)[27 + k] = v;
+    }
+    if (lane == 0) o[0] = (uint64_t)(hi - lo);
 }
 
 // DQN-buffer weights, row-major [in][out] in the caller's packed buffer (StackedQNet.pack(),
@@ -336,6 +396,13 @@ struct prisma_env {
     void* d_ingest = nullptr;            // prisma_ingest_transitions' counts and offsets (first use)
     std::vector<int32_t> ovdst;          // [T] next node (underlay id) of every (node, action), ovrow's order
     int32_t* d_targets_tab = nullptr;    // prisma_replay_targets' row[N + 1], next node[T], back action[T] (first use)
+    // scenario set (prisma_create_scenarios): the count, each replica's scenario, and with more than
+    // one scenario the replicas' image offsets (KParams::topo_off; null: one image).  d_scen_csr:
+    // prisma_scenario_stats' row[S + 1] then the replica ids by scenario, ascending
+    int32_t n_scen = 1;
+    std::vector<int32_t> scen_of;
+    uint32_t* d_topo_off = nullptr;
+    int32_t* d_scen_csr = nullptr;
 };
 
 static thread_local std::string g_err;
@@ -550,12 +617,17 @@ struct Signal {
     BigSig bs;
 };
 
+// mean inter-arrival time of a flow (s), poisson-application.cc:280-283
+static double flow_mean(const prisma_params_t* P, uint64_t rate_bps) {
+    return (double)(P->packet_size * 8u) / (double)rate_bps;
+}
+
 // Memory-resident engine (prisma_engine_mem.hip, identity overlays): topology as
 // variable-size arrays; state image = LDS part (header, counters, pending obs,
 // event-tree levels 1-2, link leaf keys) + HBM part (link records, flow leaf keys,
 // rings, ping windows, ping-back delays).  Scenario constants and ring sizing are set
 // by build_layout.
-static int layout_mem(const prisma_topology_t* T, const prisma_params_t* P, Layout& L,
+static int layout_mem(const prisma_topology_t* T, const prisma_params_t* P, const uint64_t* rates, Layout& L,
                       std::vector<unsigned char>& topo, const std::vector<int64_t>& acctx,
                       const std::vector<int32_t>& ldst, uint32_t ring_total, const Signal& SG) {
     const int N = T->n_nodes, E = T->n_links, F = T->n_flows, Lk = E + N;
@@ -600,7 +672,7 @@ static int layout_mem(const prisma_topology_t* T, const prisma_params_t* P, Layo
     memcpy(tb + L.t_fdst, T->flow_dst, 4u * (size_t)F);
     double* fm = (double*)(tb + L.t_fmean);
     for (int f = 0; f < F; ++f)                      // poisson-application.cc:280-283
-        fm[f] = (double)(P->packet_size * 8u) / (double)T->flow_rate_bps[f];
+        fm[f] = flow_mean(P, rates[f]);
     memcpy(tb + L.t_esz, SG.esz.data(), 4u * (size_t)E);
     memcpy(tb + L.t_etx, SG.etx.data(), 4u * (size_t)E);
     memcpy(tb + L.t_abtx, SG.abtx.data(), 4u * (size_t)N);
@@ -639,8 +711,10 @@ static int layout_mem(const prisma_topology_t* T, const prisma_params_t* P, Layo
     return PRISMA_OK;
 }
 
-static int build_layout(const prisma_topology_t* T, const prisma_params_t* P, Layout& L,
-                        std::vector<unsigned char>& topo) {
+// (rates: the flow rates the image is built from -- scenario 0's row; the flow LIST, and with it
+// the sizing, the instance pick and the start-event seqs, is the topology's)
+static int build_layout_one(const prisma_topology_t* T, const prisma_params_t* P, const uint64_t* rates, Layout& L,
+                            std::vector<unsigned char>& topo) {
     const int N = T->n_nodes, E0 = T->n_links, F = T->n_flows;
     if (N < 2 || N > 256) return set_err(PRISMA_ERR_CONFIG, "n_nodes must be in [2, 256] (8-bit node ids)");
     if (P->engine > PRISMA_ENGINE_MEMORY) return set_err(PRISMA_ERR_CONFIG, "engine must be PRISMA_ENGINE_AUTO, _REGISTER or _MEMORY");
@@ -674,7 +748,7 @@ static int build_layout(const prisma_topology_t* T, const prisma_params_t* P, La
                                           "(1 + max_deg rounded up to 4) must fit one 64-lane store");
     for (int f = 0; f < F; ++f) {
         if (T->flow_src[f] < 0 || T->flow_src[f] >= N || T->flow_dst[f] < 0 || T->flow_dst[f] >= N ||
-            T->flow_src[f] == T->flow_dst[f] || T->flow_rate_bps[f] == 0 ||
+            T->flow_src[f] == T->flow_dst[f] || rates[f] == 0 ||
             OP.ovi[T->flow_src[f]] < 0 || OP.ovi[T->flow_dst[f]] < 0)
             return set_err(PRISMA_ERR_CONFIG, "bad flow (flows run between overlay nodes)");
     }
@@ -924,7 +998,7 @@ static int build_layout(const prisma_topology_t* T, const prisma_params_t* P, La
     auto take = [&](uint32_t bytes) { uint32_t r = o; o = align16(o + bytes); return r; };
     L.table_bytes = (uint32_t)(N * N);
     if (engine == PRISMA_ENGINE_MEMORY)
-        return layout_mem(T, P, L, topo, acctx, ldst, tot, SG);
+        return layout_mem(T, P, rates, L, topo, acctx, ldst, tot, SG);
     // topology image
     L.topo_bytes = (uint32_t)sizeof(TopoImage) + (OP.tunnels ? 4u * (uint32_t)(N * N) : 0u);
     topo.assign(L.topo_bytes, 0);
@@ -936,7 +1010,7 @@ static int build_layout(const prisma_topology_t* T, const prisma_params_t* P, La
     memcpy(TI.fsrc, T->flow_src, 4u * F);
     memcpy(TI.fdst, T->flow_dst, 4u * F);
     for (int f = 0; f < F; ++f)                      // poisson-application.cc:280-283
-        TI.fmean[f] = (double)(P->packet_size * 8u) / (double)T->flow_rate_bps[f];
+        TI.fmean[f] = flow_mean(P, rates[f]);
     memcpy(TI.ovrow, OP.ovrow.data(), 4u * (N + 1));
     memcpy(TI.tinfo, OP.tinfo.data(), 4u * OP.T);
     for (int x = 0; x < N; ++x) TI.ovi[x] = OP.ovi[x];
@@ -1031,6 +1105,56 @@ static int build_layout(const prisma_topology_t* T, const prisma_params_t* P, La
     return PRISMA_OK;
 }
 
+// A scenario set's layout and topology images (prisma_create_scenarios; prisma_create is the set of
+// one scenario whose row is topo->flow_rate_bps).  Flow rates enter the engines through the image's
+// fmean array alone, so scenario s's image is scenario 0's with that array rebuilt from its row:
+// S whole images back to back, `stride` bytes apart, and a replica binds its own by
+// a byte offset (KParams::topo_off).  Layout::topo_bytes stays the size of one image.
+static int build_layout(const prisma_topology_t* T, const prisma_params_t* P, const prisma_scenarios_t* SC,
+                        int32_t n_replicas, Layout& L, std::vector<unsigned char>& topo, uint32_t& stride,
+                        bool images = true) {
+    if (!SC || !SC->flow_rate_bps) return set_err(PRISMA_ERR_ARG, "null scenarios or scenarios->flow_rate_bps");
+    if (!SC->scenario_of) return set_err(PRISMA_ERR_ARG, "null scenarios->scenario_of");
+    if (SC->n_scenarios < 1) return set_err(PRISMA_ERR_ARG, "scenarios->n_scenarios must be >= 1");
+    if (!T->flow_rate_bps) return set_err(PRISMA_ERR_ARG, "null topology array");
+    const int32_t S = SC->n_scenarios;
+    if (S > PRISMA_MAX_SCENARIOS)
+        return set_err(PRISMA_ERR_CONFIG, "scenarios->n_scenarios above PRISMA_MAX_SCENARIOS (65535)");
+    for (int32_t s = 0; s < S && T->n_flows >= 1; ++s)
+        for (int32_t f = 0; f < T->n_flows; ++f)
+            if (SC->flow_rate_bps[(size_t)s * T->n_flows + f] == 0)
+                return set_err(PRISMA_ERR_CONFIG, "flow_rate_bps: zero rate of flow " + std::to_string(f) +
+                                                  " in scenario " + std::to_string(s));
+    for (int32_t r = 0; r < n_replicas; ++r)
+        if (SC->scenario_of[r] < 0 || SC->scenario_of[r] >= S)
+            return set_err(PRISMA_ERR_CONFIG, "scenario_of[" + std::to_string(r) + "] = " +
+                                              std::to_string(SC->scenario_of[r]) + " is outside [0, n_scenarios = " +
+                                              std::to_string(S) + ")");
+    int rc = build_layout_one(T, P, SC->flow_rate_bps, L, topo);
+    if (rc) return rc;
+    stride = (L.topo_bytes + 255u) & ~255u;
+    if ((uint64_t)S * stride >= (1ull << 32))
+        return set_err(PRISMA_ERR_CONFIG, "scenarios->n_scenarios: the topology images of all scenarios exceed 4 GiB "
+                                          "(32-bit image offsets)");
+    // (images false: the plan functions, which report sizes only -- scenario_image_bytes)
+    if (S > 1 && images) {
+        const size_t fm_off = L.mem ? (size_t)L.t_fmean : offsetof(TopoImage, fmean);
+        topo.resize((size_t)S * stride, 0);
+        for (int32_t s = 1; s < S; ++s) {
+            unsigned char* im = topo.data() + (size_t)s * stride;
+            memcpy(im, topo.data(), L.topo_bytes);
+            double* fm = (double*)(im + fm_off);
+            for (int32_t f = 0; f < T->n_flows; ++f) fm[f] = flow_mean(P, SC->flow_rate_bps[(size_t)s * T->n_flows + f]);
+        }
+    }
+    return PRISMA_OK;
+}
+
+// device bytes of a set's topology images: one image as it is, else S strides
+static uint64_t scenario_image_bytes(const Layout& L, int32_t S, uint32_t stride) {
+    return S > 1 ? (uint64_t)S * stride : (uint64_t)L.topo_bytes;
+}
+
 // Does the env run the step kernels with the ctrl paths?  The --train echo and notify_dest paths
 // (and the ns-3 streams: flow_next) are compiled only into the instances that need them; the
 // tunnelled-overlay instances without them carry an 18-bit decision index in relay entries
@@ -1048,10 +1172,22 @@ static StepSet mlp_set(bool ctrl) { return ctrl ? kSetCtrlMlp : kSetLiteMlp; }
 extern "C" int prisma_create(const prisma_topology_t* topo, const prisma_params_t* params, int32_t n_replicas,
                              int32_t device, prisma_env_t** out) {
     if (!topo || !params || !out || n_replicas < 1) return set_err(PRISMA_ERR_ARG, "null argument or n_replicas < 1");
+    // the scenario set of one scenario: the topology's own rates, every replica in scenario 0
+    const std::vector<int32_t> zeros((size_t)n_replicas, 0);
+    const prisma_scenarios_t one = { 1, topo->flow_rate_bps, zeros.data() };
+    if (!one.flow_rate_bps) { *out = nullptr; return set_err(PRISMA_ERR_ARG, "null topology array"); }
+    return prisma_create_scenarios(topo, params, &one, n_replicas, device, out);
+}
+
+extern "C" int prisma_create_scenarios(const prisma_topology_t* topo, const prisma_params_t* params,
+                                       const prisma_scenarios_t* scenarios, int32_t n_replicas, int32_t device,
+                                       prisma_env_t** out) {
+    if (!topo || !params || !out || n_replicas < 1) return set_err(PRISMA_ERR_ARG, "null argument or n_replicas < 1");
     *out = nullptr;
     Layout L;
     std::vector<unsigned char> img;
-    int rc = build_layout(topo, params, L, img);
+    uint32_t stride = 0;
+    int rc = build_layout(topo, params, scenarios, n_replicas, L, img, stride);
     if (rc) return rc;
     int ndev = 0;
     if (!HIP_OK(hipGetDeviceCount(&ndev)) || ndev == 0) return set_err(PRISMA_ERR_DEVICE, "no HIP device");
@@ -1066,6 +1202,8 @@ extern "C" int prisma_create(const prisma_topology_t* topo, const prisma_params_
     e->device = device;
     e->R = n_replicas;
     e->lay = L;
+    e->n_scen = scenarios->n_scenarios;
+    e->scen_of.assign(scenarios->scenario_of, scenarios->scenario_of + n_replicas);
     {
         OverlayPlan OP;                      // (build_layout has validated the overlay)
         if ((rc = plan_overlay(topo, OP)) != 0) { delete e; return rc; }
@@ -1074,7 +1212,7 @@ extern "C" int prisma_create(const prisma_topology_t* topo, const prisma_params_
     }
     size_t sb = (size_t)L.state_bytes * n_replicas;
     size_t lb = (size_t)L.log_cap * L.rec_bytes * n_replicas;
-    if (!HIP_OK(hipMalloc(&e->d_state, sb)) || !HIP_OK(hipMalloc(&e->d_topo, L.topo_bytes)) ||
+    if (!HIP_OK(hipMalloc(&e->d_state, sb)) || !HIP_OK(hipMalloc(&e->d_topo, img.size())) ||
         !HIP_OK(hipMalloc(&e->d_log, lb)) ||
         !HIP_OK(hipMalloc((void**)&e->d_cnt, sizeof(prisma_counters_t) * n_replicas)) ||
         !HIP_OK(hipMalloc((void**)&e->d_lay, sizeof(Layout)))) {
@@ -1125,7 +1263,31 @@ extern "C" int prisma_create(const prisma_topology_t* topo, const prisma_params_
         prisma_destroy(e);
         return set_err(PRISMA_ERR_NOMEM, "hipMalloc of the spare images failed");
     }
-    if (!HIP_OK(hipMemcpy(e->d_topo, img.data(), L.topo_bytes, hipMemcpyHostToDevice)) ||
+    {
+        // prisma_scenario_stats' CSR: row[S + 1], then the replicas of scenario 0, 1, ... each in
+        // ascending replica index
+        const int32_t S = e->n_scen, R = n_replicas;
+        std::vector<int32_t> csr((size_t)S + 1 + (size_t)R, 0);
+        for (int32_t r = 0; r < R; ++r) csr[(size_t)e->scen_of[r] + 1]++;
+        for (int32_t s = 0; s < S; ++s) csr[(size_t)s + 1] += csr[s];
+        std::vector<int32_t> fill(csr.begin(), csr.begin() + S);
+        for (int32_t r = 0; r < R; ++r) csr[(size_t)S + 1 + (size_t)fill[e->scen_of[r]]++] = r;
+        if (!HIP_OK(hipMalloc((void**)&e->d_scen_csr, csr.size() * sizeof(int32_t))) ||
+            !HIP_OK(hipMemcpy(e->d_scen_csr, csr.data(), csr.size() * sizeof(int32_t), hipMemcpyHostToDevice))) {
+            prisma_destroy(e);
+            return set_err(PRISMA_ERR_NOMEM, "hipMalloc of the scenario CSR failed");
+        }
+    }
+    if (e->n_scen > 1) {
+        std::vector<uint32_t> off((size_t)n_replicas);
+        for (int32_t r = 0; r < n_replicas; ++r) off[r] = (uint32_t)e->scen_of[r] * stride;
+        if (!HIP_OK(hipMalloc((void**)&e->d_topo_off, 4u * off.size())) ||
+            !HIP_OK(hipMemcpy(e->d_topo_off, off.data(), 4u * off.size(), hipMemcpyHostToDevice))) {
+            prisma_destroy(e);
+            return set_err(PRISMA_ERR_NOMEM, "hipMalloc of the replicas' image offsets failed");
+        }
+    }
+    if (!HIP_OK(hipMemcpy(e->d_topo, img.data(), img.size(), hipMemcpyHostToDevice)) ||
         !HIP_OK(hipMemcpy(e->d_lay, &L, sizeof(Layout), hipMemcpyHostToDevice)) ||
         !HIP_OK(hipMemset(e->d_log, 0, lb)) ||
         !HIP_OK(hipMemset(e->d_cnt, 0, sizeof(prisma_counters_t) * n_replicas))) {
@@ -1173,6 +1335,7 @@ static KParams base_params(prisma_env_t* e) {
     P.R = e->R;
     P.spare = e->d_spare;
     P.rng = e->d_rng;
+    P.topo_off = e->d_topo_off;
     return P;
 }
 
@@ -1556,9 +1719,54 @@ extern "C" int prisma_state_bytes(prisma_env_t* e, uint32_t* state_bytes, uint32
 
 extern "C" int prisma_plan(const prisma_topology_t* topo, const prisma_params_t* params, prisma_plan_t* out) {
     if (!topo || !params || !out) return set_err(PRISMA_ERR_ARG, "null argument");
+    const int32_t zero = 0;
+    const prisma_scenarios_t one = { 1, topo->flow_rate_bps, &zero };
+    if (!one.flow_rate_bps) return set_err(PRISMA_ERR_ARG, "null topology array");
+    return prisma_plan_scenarios(topo, params, &one, 1, out);
+}
+
+extern "C" int prisma_plan_scenario_images(const prisma_topology_t* topo, const prisma_params_t* params,
+                                           const prisma_scenarios_t* scenarios, int32_t n_replicas,
+                                           prisma_scenario_plan_t* out) {
+    if (!topo || !params || !out || n_replicas < 1) return set_err(PRISMA_ERR_ARG, "null argument or n_replicas < 1");
     Layout L;
     std::vector<unsigned char> img;
-    int rc = build_layout(topo, params, L, img);
+    uint32_t stride = 0;
+    int rc = build_layout(topo, params, scenarios, n_replicas, L, img, stride, false);
+    if (rc) return rc;
+    out->topo_bytes = scenario_image_bytes(L, scenarios->n_scenarios, stride);
+    out->image_bytes = L.topo_bytes;
+    out->n_scenarios = scenarios->n_scenarios;
+    return PRISMA_OK;
+}
+
+extern "C" int prisma_scenario_info(prisma_env_t* e, int32_t* n_scenarios, int32_t* scenario_of_out) {
+    if (!e) return set_err(PRISMA_ERR_ARG, "null env");
+    if (n_scenarios) *n_scenarios = e->n_scen;
+    if (scenario_of_out) memcpy(scenario_of_out, e->scen_of.data(), sizeof(int32_t) * e->scen_of.size());
+    return PRISMA_OK;
+}
+
+extern "C" int prisma_scenario_stats(prisma_env_t* e, prisma_scenario_stats_t* out_device, void* stream) {
+    if (!e || !out_device) return set_err(PRISMA_ERR_ARG, "prisma_scenario_stats: null env or out_device");
+    (void)hipSetDevice(e->device);
+    const int32_t S = e->n_scen, R = e->R;
+    hipLaunchKernelGGL(prisma_scenario_stats_kernel, dim3((unsigned)S), dim3(kWave), 0, (hipStream_t)stream,
+                       (const prisma_counters_t*)e->d_cnt, (const int32_t*)e->d_scen_csr,
+                       (const int32_t*)(e->d_scen_csr + S + 1), R, out_device);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess)
+        return set_err(PRISMA_ERR_LAUNCH, std::string("scenario stats launch failed: ") + hipGetErrorString(err));
+    return PRISMA_OK;
+}
+
+extern "C" int prisma_plan_scenarios(const prisma_topology_t* topo, const prisma_params_t* params,
+                                     const prisma_scenarios_t* scenarios, int32_t n_replicas, prisma_plan_t* out) {
+    if (!topo || !params || !out || n_replicas < 1) return set_err(PRISMA_ERR_ARG, "null argument or n_replicas < 1");
+    Layout L;
+    std::vector<unsigned char> img;
+    uint32_t stride = 0;
+    int rc = build_layout(topo, params, scenarios, n_replicas, L, img, stride, false);
     if (rc) return rc;
     out->state_bytes = L.state_bytes;
     out->lds_bytes = L.lds_bytes;
@@ -1586,5 +1794,7 @@ extern "C" void prisma_destroy(prisma_env_t* e) {
     if (e->d_rng) (void)hipFree(e->d_rng);
     if (e->d_ingest) (void)hipFree(e->d_ingest);
     if (e->d_targets_tab) (void)hipFree(e->d_targets_tab);
+    if (e->d_topo_off) (void)hipFree(e->d_topo_off);
+    if (e->d_scen_csr) (void)hipFree(e->d_scen_csr);
     delete e;
 }

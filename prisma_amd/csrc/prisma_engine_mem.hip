@@ -404,7 +404,8 @@ __device__ __forceinline__ void mem_bind(Sim& S, MemSt& R, const KParams& P, con
                                          int lane) {
     CLayout& LC = *(CLayout*)P.lay;
     unsigned char* img = P.state + (size_t)r * LC.state_bytes;
-    sim_bind(S, lv, lds, P.topo, P.log + (size_t)r * LC.log_cap * LC.rec_bytes, LC.replica_base + (uint32_t)r, lane);
+    const unsigned char* topo = replica_topo(P, r);
+    sim_bind(S, lv, lds, topo, P.log + (size_t)r * LC.log_cap * LC.rec_bytes, LC.replica_base + (uint32_t)r, lane);
     S.mem = true;
     S.tun = false;
     S.ring = (uint32_t*)(img + LC.s_ring);
@@ -414,7 +415,7 @@ __device__ __forceinline__ void mem_bind(Sim& S, MemSt& R, const KParams& P, con
     S.table = P.table;
     S.table_g = P.table;
     S.tab_lds = false;
-    const CAS unsigned char* tb = (const CAS unsigned char*)P.topo;
+    const CAS unsigned char* tb = (const CAS unsigned char*)topo;
     S.m_rowptr = (const CAS int32_t*)(tb + LC.t_rowptr);
     S.m_ldst = (const CAS int32_t*)(tb + LC.t_ldst);
     S.m_lrev = (const CAS int32_t*)(tb + LC.t_lrev);

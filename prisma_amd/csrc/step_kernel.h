@@ -120,7 +120,7 @@ __device__ unsigned long long g_wave_times[4 * 65536];
     stage_in(lds, P, r, lane, R);                                                                       \
     __syncthreads();                                                                                    \
     Sim S;                                                                                              \
-    sim_bind(S, lv, lds, P.topo, P.log + (size_t)r * LC.log_cap * LC.rec_bytes, LC.replica_base + (uint32_t)r, lane); \
+    sim_bind(S, lv, lds, replica_topo(P, r), P.log + (size_t)r * LC.log_cap * LC.rec_bytes, LC.replica_base + (uint32_t)r, lane); \
     S.tun = TUN;                                                                                        \
     S.ctrl = CTRL;                                                                                      \
     S.lanel = PRISMA_LANE_LINKS != 0 && (FUSED_) && (EXPL_) == 0 && LS == 1 && FS <= 4 && !TUN && !CTRL; \

@@ -117,13 +117,23 @@ class _Plan(C.Structure):
                 ("flow_slots", C.c_int32), ("link_slots", C.c_int32), ("engine", C.c_uint32)]
 
 
+class _Scenarios(C.Structure):
+    """prisma_scenarios_t: the flow rates of S scenarios and each replica's scenario (host arrays)."""
+    _fields_ = [("n_scenarios", C.c_int32), ("flow_rate_bps", C.c_void_p), ("scenario_of", C.c_void_p)]
+
+
+class _ScenarioPlan(C.Structure):
+    _fields_ = [("topo_bytes", C.c_uint64), ("image_bytes", C.c_uint32), ("n_scenarios", C.c_int32)]
+
+
 EXPORTS = [
     "prisma_abi_version", "prisma_last_error", "prisma_build_id", "prisma_create", "prisma_reset", "prisma_step", "prisma_run",
     "prisma_run_explore", "prisma_action_history_layout", "prisma_run_explore_smart", "prisma_run_stochastic",
     "prisma_read_counters", "prisma_counters_device", "prisma_log_view", "prisma_copy_log",
     "prisma_copy_counters", "prisma_gather_records", "prisma_state_bytes", "prisma_plan", "prisma_destroy",
     "prisma_compact_pending", "prisma_expand_actions", "prisma_kernel_info", "prisma_ingest_transitions",
-    "prisma_replay_targets",
+    "prisma_replay_targets", "prisma_create_scenarios", "prisma_plan_scenarios", "prisma_plan_scenario_images",
+    "prisma_scenario_info", "prisma_scenario_stats",
 ]
 
 _lib = None
@@ -201,6 +211,19 @@ def load_library(path: str = None):
     L.prisma_state_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.prisma_plan.restype = C.c_int
     L.prisma_plan.argtypes = [C.POINTER(_Topo), C.POINTER(_Params), C.POINTER(_Plan)]
+    L.prisma_create_scenarios.restype = C.c_int
+    L.prisma_create_scenarios.argtypes = [C.POINTER(_Topo), C.POINTER(_Params), C.POINTER(_Scenarios), C.c_int32,
+                                          C.c_int32, C.POINTER(C.c_void_p)]
+    L.prisma_plan_scenarios.restype = C.c_int
+    L.prisma_plan_scenarios.argtypes = [C.POINTER(_Topo), C.POINTER(_Params), C.POINTER(_Scenarios), C.c_int32,
+                                        C.POINTER(_Plan)]
+    L.prisma_plan_scenario_images.restype = C.c_int
+    L.prisma_plan_scenario_images.argtypes = [C.POINTER(_Topo), C.POINTER(_Params), C.POINTER(_Scenarios), C.c_int32,
+                                              C.POINTER(_ScenarioPlan)]
+    L.prisma_scenario_info.restype = C.c_int
+    L.prisma_scenario_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
+    L.prisma_scenario_stats.restype = C.c_int
+    L.prisma_scenario_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.prisma_destroy.restype = None
     L.prisma_destroy.argtypes = [C.c_void_p]
     if L.prisma_abi_version() != ABI_VERSION:
@@ -251,14 +274,41 @@ def _params_struct(params: dict) -> _Params:
                       for k, _ in _Params._fields_})
 
 
-def plan(topo: Topology, params: dict) -> dict:
-    """prisma_plan: validate a scenario and report its per-replica footprint (no device needed)."""
+def _scenarios_struct(scenarios, scenario_of, n_replicas: int, n_flows: int, replica_base: int = 0):
+    """prisma_scenarios_t from a scenarios.ScenarioSet (or a uint64 [S, F] array of rates) and an
+    int32 [n_replicas] assignment (default: ScenarioSet.assign's round robin by GLOBAL replica id,
+    (replica_base + r) mod S, so a shard agrees with the unsharded env)."""
+    rates = np.ascontiguousarray(getattr(scenarios, "rates", scenarios), dtype=np.uint64)
+    if rates.ndim != 2 or rates.shape[1] != n_flows:
+        raise PrismaError(f"scenarios: rates must be a uint64 [S, {n_flows}] array")
+    if scenario_of is None:
+        scenario_of = (int(replica_base) + np.arange(n_replicas)) % max(rates.shape[0], 1)
+    sc = np.ascontiguousarray(scenario_of, dtype=np.int32)
+    if sc.shape != (n_replicas,):
+        raise PrismaError(f"scenario_of must have n_replicas = {n_replicas} entries")
+    return _Scenarios(rates.shape[0], rates.ctypes.data, sc.ctypes.data), [rates, sc]
+
+
+def plan(topo: Topology, params: dict, scenarios=None, scenario_of=None, n_replicas: int = 1) -> dict:
+    """prisma_plan: validate a scenario and report its per-replica footprint (no device needed).
+    scenarios (a scenarios.ScenarioSet or uint64 [S, F] rates; scenario_of int32 [n_replicas]):
+    prisma_plan_scenarios, with the set's validation, plus topo_bytes -- the device bytes of all
+    scenarios' topology images --, image_bytes and n_scenarios (prisma_plan_scenario_images)."""
     L = load_library()
     t, keep = _topo_struct(topo)
     p = _params_struct(params)
     out = _Plan()
-    _check(L.prisma_plan(C.byref(t), C.byref(p), C.byref(out)))
-    return {k: int(getattr(out, k)) for k, _ in _Plan._fields_}
+    if scenarios is None:
+        _check(L.prisma_plan(C.byref(t), C.byref(p), C.byref(out)))
+        return {k: int(getattr(out, k)) for k, _ in _Plan._fields_}
+    sc, keep2 = _scenarios_struct(scenarios, scenario_of, int(n_replicas), topo.n_flows,
+                                  params.get("replica_base", 0))
+    _check(L.prisma_plan_scenarios(C.byref(t), C.byref(p), C.byref(sc), int(n_replicas), C.byref(out)))
+    sp = _ScenarioPlan()
+    _check(L.prisma_plan_scenario_images(C.byref(t), C.byref(p), C.byref(sc), int(n_replicas), C.byref(sp)))
+    res = {k: int(getattr(out, k)) for k, _ in _Plan._fields_}
+    res.update({k: int(getattr(sp, k)) for k, _ in _ScenarioPlan._fields_})
+    return res
 
 
 def step_kernel_names(ki: dict, pl: dict) -> dict:
@@ -285,9 +335,15 @@ def step_kernel_names(ki: dict, pl: dict) -> dict:
 
 
 class PrismaEngine:
-    """R replicas of one scenario on one MI355X (device memory owned by the library)."""
+    """R replicas of one scenario on one MI355X (device memory owned by the library).
 
-    def __init__(self, topo: Topology, params: dict, n_replicas: int, device: int = 0):
+    scenarios (a scenarios.ScenarioSet, or uint64 [S, F] rates) with scenario_of (int32
+    [n_replicas], each in [0, S); default round robin by global id, (replica_base + r) mod S): replica r reads the flow rates of scenario
+    scenario_of[r] instead of topo's (prisma_create_scenarios); `topo` is then the set's structure,
+    by convention scenario 0's topology."""
+
+    def __init__(self, topo: Topology, params: dict, n_replicas: int, device: int = 0, scenarios=None,
+                 scenario_of=None):
         import torch
         if not torch.cuda.is_available():
             raise PrismaError("PrismaEngine needs a HIP device (no CPU fallback)")
@@ -300,9 +356,23 @@ class PrismaEngine:
         t, self._keep = _topo_struct(topo)
         p = _params_struct(params)
         h = C.c_void_p()
+        if scenarios is None and scenario_of is not None:
+            raise PrismaError("scenario_of needs scenarios")
         with torch.cuda.device(self.device):
-            _check(L.prisma_create(C.byref(t), C.byref(p), self.R, self.device, C.byref(h)))
+            if scenarios is None:
+                _check(L.prisma_create(C.byref(t), C.byref(p), self.R, self.device, C.byref(h)))
+            else:
+                sc, _keep = _scenarios_struct(scenarios, scenario_of, self.R, topo.n_flows,
+                                              params.get("replica_base", 0))
+                _check(L.prisma_create_scenarios(C.byref(t), C.byref(p), C.byref(sc), self.R, self.device,
+                                                 C.byref(h)))
         self.h = h
+        ns = C.c_int32()
+        so = np.zeros(self.R, dtype=np.int32)
+        _check(L.prisma_scenario_info(self.h, C.byref(ns), so.ctypes.data))
+        self.n_scenarios = int(ns.value)
+        self.scenario_of_host = so
+        self.scenario_of = torch.from_numpy(so).to(self.torch_device)
         lv = _LogView()
         _check(L.prisma_log_view(self.h, C.byref(lv)))
         self.W = int(lv.obs_width)
@@ -527,6 +597,18 @@ class PrismaEngine:
         out = np.zeros(self.R, dtype=COUNTERS_DTYPE)
         _check(_lib.prisma_read_counters(self.h, out.ctypes.data, _stream_handle(stream)))
         return out
+
+    def scenario_stats(self, stream=None):
+        """prisma_scenario_stats: per-scenario sums of the replicas' counters, one launch on torch's
+        current stream (or `stream`), no host read.  A device uint8 tensor [n_scenarios, 248]:
+        rows of scenarios.STATS_DTYPE (``.cpu().numpy().view(STATS_DTYPE)``); the f64 sums are in
+        the fixed order scenarios.stats_sum restates."""
+        import torch
+        from .scenarios import STATS_DTYPE
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.device)):
+            buf = torch.empty((self.n_scenarios, STATS_DTYPE.itemsize), dtype=torch.uint8, device=self.torch_device)
+        _check(_lib.prisma_scenario_stats(self.h, buf.data_ptr(), _stream_handle(stream)))
+        return buf
 
     def counters_tensor(self, stream=None):
         """Device copy of the counters as a torch uint8 tensor [R, 144] (for device-side use / collectives)."""

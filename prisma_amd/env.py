@@ -60,10 +60,24 @@ def decode_records(rec: torch.Tensor, W: int) -> dict:
 
 class VecRoutingEnv:
     def __init__(self, topology="abilene", tm_index: int = 0, load_factor: float = 1.0,
-                 n_replicas: int = 1024, device: int = 0, topo: Optional[Topology] = None, **params):
-        self.topo = topo if topo is not None else Topology.example(topology, tm_index, load_factor)
+                 n_replicas: int = 1024, device: int = 0, topo: Optional[Topology] = None, scenarios=None,
+                 scenario_of=None, **params):
+        """scenarios: a scenarios.ScenarioSet -- replica r runs the traffic of scenario
+        scenario_of[r] (int32 [n_replicas]; default ``scenarios.assign(n_replicas, replica_base=...)``,
+        round robin by global id).  env.topo is then scenario 0's topology and env.scenarios the set;
+        step, run, transitions, ingest_transitions and train_fused work unchanged."""
+        self.scenarios = scenarios
+        if scenarios is not None:
+            self.topo = scenarios.topos[0]
+            if scenario_of is None:
+                scenario_of = scenarios.assign(n_replicas, replica_base=int(params.get("replica_base", 0)))
+        else:
+            if scenario_of is not None:
+                raise ValueError("scenario_of needs scenarios")
+            self.topo = topo if topo is not None else Topology.example(topology, tm_index, load_factor)
         self.params = engine_params(self.topo, **params)
-        self.engine = PrismaEngine(self.topo, self.params, n_replicas, device)
+        self.engine = PrismaEngine(self.topo, self.params, n_replicas, device, scenarios=scenarios,
+                                   scenario_of=scenario_of)
         self.R = n_replicas
         self.W = self.engine.W
         self.device = self.engine.torch_device
@@ -153,6 +167,17 @@ class VecRoutingEnv:
 
     def counters(self) -> np.ndarray:
         return self.engine.counters()
+
+    def scenario_stats(self) -> dict:
+        """Per-scenario sums of the replicas' counters (PrismaEngine.scenario_stats: one launch, then
+        one host read of 248 B per scenario) -- every field of scenarios.STATS_DTYPE as a numpy array
+        [n_scenarios] -- plus avg_e2e_delay, loss_ratio and avg_cost per scenario
+        (scenarios.derived_stats).  An env without a scenario set has one scenario."""
+        from .scenarios import STATS_DTYPE, derived_stats
+        st = self.engine.scenario_stats().cpu().numpy().reshape(-1).view(STATS_DTYPE)
+        out = {k: st[k].copy() for k in STATS_DTYPE.names}
+        out.update(derived_stats(st))
+        return out
 
     def _counter_fields(self) -> dict:
         """dec_count, now_ns, episode and error bits of every replica (device int64 [R])."""
